@@ -12,6 +12,17 @@ batch is fixed, `value` is the whole-job samples/sec across all ranks.
 Launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, settles + warms up, times the K steps and prints one
+JSON result line.  `--dump-outputs DIR` additionally writes the state the
+last timed step left (parameters, momentum, BN running stats, loss) as
+DIR/<name>.npy.  Model init and the data pool are seeded, and with this
+option the model is rewound to its seeded initial state just before the
+last timed step, so the dump is what that step makes of inputs that are
+identical from run to run and two builds can be compared output for output
+(momentum starts at zero there, so `momentum` is the step's gradient plus
+weight decay).  `--full` is reserved for secondary measurements and checks
+(none yet): they must never run in a plain run.
 """
 import argparse
 import json
@@ -40,7 +51,13 @@ if os.path.isdir(_MDB) and os.environ.get('FEDTORCH_MIOPEN_DB', '1') == '1':
     for _sub, _dst in (('udb', _d), ('cache', _c)):
         _src = os.path.join(_MDB, _sub)
         if os.path.isdir(_src):
-            shutil.copytree(_src, _dst, dirs_exist_ok=True)
+            # contents only: a read-only checkout must still stage a
+            # WRITABLE copy (MIOpen opens its sqlite cache read-write and
+            # fails every conv with miopenStatusInternalError otherwise)
+            shutil.copytree(_src, _dst, dirs_exist_ok=True,
+                            copy_function=shutil.copyfile)
+            for _root, _, _ in os.walk(_dst):
+                os.chmod(_root, 0o755)
     if os.path.isdir(_d):
         os.environ.setdefault('MIOPEN_USER_DB_PATH', _d)
     if os.path.isdir(_c):
@@ -97,7 +114,37 @@ def parse():
                    help='sync algorithm: plain FedAvg or FedCOMGATE '
                         '(FedGATE + top-k compression / quantization, '
                         'BASELINE config 3)')
+    p.add_argument('--dump-outputs', dest='dump_outputs', type=str,
+                   default=None, metavar='DIR',
+                   help='after the timed steps write what the last timed '
+                        'step left behind (parameters, momentum, BN running '
+                        'stats, loss) as DIR/<name>.npy (fp32)')
+    p.add_argument('--full', action='store_true',
+                   help='also run every secondary measurement or check.  A '
+                        'plain run does only what the headline figure needs; '
+                        'the benchmark has no secondary measurements yet, so '
+                        'today --full adds nothing.')
     return p.parse_args()
+
+
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor-or-None} as dirname/<name>.npy in fp32.  An array
+    over its equal share of DUMP_CAP_BYTES is reduced to a fixed, seeded
+    sample of its elements (same indices every run)."""
+    import numpy as np
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_CAP_BYTES // 4 // max(len(arrays), 1)  # fp32 elements each
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            idx = np.random.default_rng(1234).choice(a.size, share,
+                                                     replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def main():
@@ -181,6 +228,17 @@ def main():
         loss.backward()
         client.optimizer.step(apply_lr=True, apply_in_momentum=True,
                               apply_out_momentum=False)
+        return loss
+
+    def train_state():
+        """every tensor the timed path carries from one step to the next"""
+        bufs = (client.arena.flat, client.arena.buf_flat, client.model_server,
+                getattr(client, 'model_delta', None),
+                getattr(client, 'model_memory', None))
+        return [t for t in bufs if t is not None]
+
+    # seeded initial state (momentum starts at zero), kept for --dump-outputs
+    seeded = [t.clone() for t in train_state()] if b.dump_outputs else None
 
     use_graph = on_gpu and b.graph != 'off'
     if use_graph:
@@ -241,9 +299,10 @@ def main():
             static_y.copy_(ys[i % pool_n])
             graph.replay()
             graph2.replay()
+            return loss  # static tensor the captured graph rewrites
     else:
         def local_step(i):
-            inner(xs[i % pool_n], ys[i % pool_n])
+            return inner(xs[i % pool_n], ys[i % pool_n])
 
     def sync():
         args.comm_time.append(0.0)
@@ -260,11 +319,15 @@ def main():
                              work=client.work)
         client.arena.sync_half()
 
-    def run(n_steps):
-        for s in range(1, n_steps + 1):
-            local_step(s)
+    def run(n_steps, first=1):
+        """steps first..n_steps of a sequence that syncs at every TAU-th;
+        returns the loss tensor of the last step (None for no steps)"""
+        last = None
+        for s in range(first, n_steps + 1):
+            last = local_step(s)
             if s % TAU == 0:
                 sync()
+        return last
 
     # ---- settle (untimed setup, independent of --warmup) ----
     # A fresh box pays one-time costs on the FIRST execution of each
@@ -306,10 +369,30 @@ def main():
 
     # ---- timed ----
     t0 = time.perf_counter()
-    run(b.steps)
+    if seeded is None:
+        last_loss = run(b.steps)
+    else:
+        # --dump-outputs: training amplifies the last-bit noise of float
+        # atomics by orders of magnitude within ~20 steps, so two runs only
+        # agree on a step whose inputs agree.  Rewind to the seeded initial
+        # state (a few device copies, no host sync) before the LAST timed
+        # step; the dump is what that step makes of fixed inputs.
+        run(b.steps - 1)
+        for dst, src in zip(train_state(), seeded):
+            dst.copy_(src)
+        if client.optimizer._in_buf is not None:
+            client.optimizer._in_buf.zero_()
+        client.arena.sync_half()
+        last_loss = run(b.steps, first=b.steps)
     if on_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if b.dump_outputs and rank == 0:
+        dump_outputs(b.dump_outputs, {
+            'params': client.arena.flat,
+            'momentum': client.optimizer._in_buf,
+            'bn_running_stats': client.arena.buf_flat,
+            'loss': last_loss})
     # MAX over ranks
     t = torch.tensor([elapsed], dtype=torch.float64)
     if dist.is_initialized():
@@ -494,6 +577,9 @@ def run_packed_bench(b, client, args, xs, ys, pool_n, world, rank, on_gpu):
     if on_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if b.dump_outputs and rank == 0:
+        dump_outputs(b.dump_outputs, {
+            'server': server, 'client_params': state, 'client_momentum': mom})
     t = torch.tensor([elapsed], dtype=torch.float64)
     if dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -551,17 +551,20 @@ def test_mfma_tile_gemm():
         (D - ref).abs().max().item()
 
 
-def test_bench_contract():
-    """bench.py emits the driver-contract JSON line and runs the native
-    path (subprocess, tiny step count)."""
+def test_bench_contract(tmp_path):
+    """bench.py emits the driver-contract JSON line, runs the native
+    path (subprocess, tiny step count) and --dump-outputs writes the final
+    state of the timed path as fp32 .npy files."""
     import json
     import subprocess
     import sys
     import os
+    import numpy as np
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = str(tmp_path / 'dump')
     out = subprocess.run(
         [sys.executable, os.path.join(repo, 'bench.py'), '--steps', '12',
-         '--warmup', '4', '--batch', '64'],
+         '--warmup', '4', '--batch', '64', '--dump-outputs', dump],
         capture_output=True, text=True, timeout=420, cwd=repo)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
@@ -572,6 +575,18 @@ def test_bench_contract():
     assert d['dtype'] == 'bf16'
     assert d['data'] == 'synthetic'
     assert d['config']['model'] == 'resnet20'
+    assert d['steps'] == 12
+    assert abs(d['ms_per_step'] * d['value'] - 64 * 1e3) < 1e-3 * 64 * 1e3
+    names = sorted(os.listdir(dump))
+    assert names == ['bn_running_stats.npy', 'loss.npy', 'momentum.npy',
+                     'params.npy']
+    total = 0
+    for n in names:
+        a = np.load(os.path.join(dump, n))
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(os.path.join(dump, 'params.npy')).size > 250000
 
 
 @pytest.mark.parametrize('C,W', [(16, 32), (32, 16), (64, 8)])

@@ -147,6 +147,44 @@ def test_bench_two_rank_cpu_contract():
     assert d['value'] > 0
 
 
+def test_bench_dump_outputs_repeatable_cpu(tmp_path):
+    """`--dump-outputs DIR` writes the state the last timed step left as
+    fp32 .npy files; the same arguments give the same inputs, so two runs
+    dump the same arrays (bit-exact on CPU).  `--steps` sets the number of
+    timed steps, `ms_per_step` is reported, `--full` is accepted."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for tag, extra in (('a', []), ('b', ['--full'])):
+        dump = str(tmp_path / tag)
+        out = subprocess.run(
+            [sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '1',
+             '--steps', '11', '--warmup', '1', '--batch', '8',
+             '--dump-outputs', dump] + extra,
+            capture_output=True, text=True, timeout=600, cwd=repo)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d['steps'] == 11
+        assert d['ms_per_step'] > 0
+        assert abs(d['value'] * d['ms_per_step'] - 8e3) < 8.0
+        dumps.append({n: np.load(os.path.join(dump, n))
+                      for n in sorted(os.listdir(dump))})
+    a, b = dumps
+    assert sorted(a) == ['bn_running_stats.npy', 'loss.npy', 'momentum.npy',
+                         'params.npy']
+    assert sorted(b) == sorted(a)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        assert np.array_equal(a[n], b[n]), n
+    assert np.abs(a['momentum.npy']).max() > 0  # training really stepped
+
+
 def test_accuracy_and_per_class_oracle():
     """metrics vs hand-computed values (reference `metrics.py:50-91`)."""
     import torch
