@@ -14,7 +14,13 @@ Default GPU training path for the CIFAR ResNet body convs (Co == Ci,
 * deferred BN backward (opt-in): the BN's elementwise dx pass runs
   inside the dgrad staging, handed off through a data_ptr-keyed side
   table (python tensor attrs do not survive the autograd engine's
-  rewrapping).
+  rewrapping);
+* stride-2 transition backward (opt-in, FEDTORCH_MFMA_S2_BWD=1):
+  `hip/convs2bwd.h` conv3x3s2_dgrad_k (parity-class implicit GEMM) and
+  conv3x3s2_wrw_k (column-parity-split staging) replace the one combined
+  MIOpen call of _Conv3x3S2BNFn.backward — 20.7 vs 30.0 us (16->32) and
+  22.5 vs 22.0 us (32->64) of device time per conv; not resolved in the
+  flagship bench, hence off by default (profiles/s2bwd_notes.md).
 
 Anything else falls back to stock F.conv2d autograd.  Per-call evidence:
 profiles/r02_bench_notes.md; kernel details: hip/README.md.
@@ -66,6 +72,12 @@ _DGRAD_ENABLED = os.environ.get('FEDTORCH_MFMA_DGRAD', '1') == '1'
 # side kernels + the 2 extra tensors the transform stages; default OFF,
 # capability kept (tests pin deferred == eager gradients).
 _BNDEFER_ENABLED = os.environ.get('FEDTORCH_BN_DEFER', '0') == '1'
+# MFMA backward of the two 3x3/stride-2 transition convs
+# (hip/convs2bwd.h): parity-class dgrad + parity-plane wrw replace the one
+# combined MIOpen call in _Conv3x3S2BNFn.backward.  Opt-in
+# (FEDTORCH_MFMA_S2_BWD=1); per-call and in-bench figures in
+# profiles/s2bwd_notes.md.
+_S2BWD_ENABLED = os.environ.get('FEDTORCH_MFMA_S2_BWD', '0') == '1'
 _BNBWD_TAGS = {}
 
 
@@ -167,7 +179,8 @@ class _Conv3x3S2BNFn(torch.autograd.Function):
     """stride-2 transition conv (16->32, 32->64) with the fused BN-stats
     epilogue; backward = ONE combined MIOpen call (these run once per
     step each — the fwd CK solver + the following BN's stats pass are
-    the pool)."""
+    the pool), or with _S2BWD_ENABLED the conv3x3s2_dgrad /
+    conv3x3s2_wrw kernels (hip/convs2bwd.h)."""
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -203,6 +216,11 @@ class _Conv3x3S2BNFn(torch.autograd.Function):
             D = coefs[2].view(1, C, 1, 1)
             dy = (g.float() * A + B + D * xbn.float()).bfloat16() \
                 .contiguous(memory_format=_CL)
+        if _S2BWD_ENABLED and ops.hip_available() and not ops.FORCE_EAGER:
+            dx = ops._C.conv3x3s2_dgrad(dy, weight) \
+                if ctx.needs_input_grad[0] else None
+            dw = ops._C.conv3x3s2_wrw(dy, x)
+            return dx, dw
         dx, dw, _ = torch.ops.aten.convolution_backward(
             dy, x, weight, None, [2, 2], [1, 1], [1, 1], False, [0, 0],
             1, [bool(ctx.needs_input_grad[0]), True, False])

@@ -17,6 +17,7 @@
 #include "convwrw.h"
 #include "convwrw2.h"
 #include "convfwd.h"
+#include "convs2bwd.h"
 
 #define CHK(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
 #define STREAM at::hip::getCurrentHIPStream().stream()
@@ -1188,6 +1189,103 @@ std::vector<torch::Tensor> conv3x3_dgrad_bn(
   return {dx, dyc};
 }
 
+// ==========================================================================
+// MFMA backward of the 3x3/s2 transition convs (convs2bwd.h)
+// ==========================================================================
+static inline void s2bwd_check(const char* who, const torch::Tensor& dy,
+                               const torch::Tensor& other, int Ci, int Co,
+                               int HI, int WI) {
+  TORCH_CHECK(dy.is_cuda() && other.is_cuda() && dy.dim() == 4 &&
+                  other.dim() == 4,
+              who, ": 4D GPU tensors");
+  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  other.is_contiguous(at::MemoryFormat::ChannelsLast),
+              who, ": channels_last only");
+  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
+                  other.scalar_type() == torch::kBFloat16,
+              who, ": bf16 only");
+  const bool ok = (Co == 2 * Ci) && ((Ci == 16 && WI == 32) ||
+                                     (Ci == 32 && WI == 16));
+  TORCH_CHECK(ok, who, ": unsupported (Ci,Co,WI)=", Ci, ",", Co, ",", WI);
+  TORCH_CHECK(HI > 0 && HI % 16 == 0, who, ": H_in % 16 != 0");
+}
+
+torch::Tensor conv3x3s2_dgrad(torch::Tensor dy, torch::Tensor w) {
+  TORCH_CHECK(dy.dim() == 4 && w.dim() == 4,
+              "conv3x3s2_dgrad: 4D GPU tensors");
+  const int N = dy.size(0), Co = dy.size(1);
+  const int HI = dy.size(2) * 2, WI = dy.size(3) * 2;
+  const int Ci = w.size(1);
+  s2bwd_check("conv3x3s2_dgrad", dy, w, Ci, Co, HI, WI);
+  TORCH_CHECK(w.size(0) == Co && w.size(2) == 3 && w.size(3) == 3,
+              "conv3x3s2_dgrad: w must be [Co, Ci, 3, 3]");
+  auto dx = torch::empty(
+      {N, Ci, HI, WI},
+      dy.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const __hip_bfloat16* dyp =
+      reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr());
+  const __hip_bfloat16* wp =
+      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
+  __hip_bfloat16* dxp = reinterpret_cast<__hip_bfloat16*>(dx.data_ptr());
+  if (N == 0) return dx;
+  if (Ci == 16)   // 8 input rows per workgroup
+    hipLaunchKernelGGL((conv3x3s2_dgrad_k<16, 32, 16, 32>),
+                       dim3(N * (HI / 8)), dim3(FT_BLOCK), 0, STREAM, dyp,
+                       wp, dxp, N, HI);
+  else            // 16 input rows x 2 ci tiles
+    hipLaunchKernelGGL((conv3x3s2_dgrad_k<32, 64, 16, 16>),
+                       dim3(N * (HI / 16) * 2), dim3(FT_BLOCK), 0, STREAM,
+                       dyp, wp, dxp, N, HI);
+  return dx;
+}
+
+// supertile streams launched at most.  Every stream emits one fp32 copy of
+// dw as partials (18 KB for 16->32, 72 KB for 32->64), so the cap trades
+// partial traffic against busy CUs; measured best at N=256: 256 / 128
+// (profiles/s2bwd_notes.md).  Exposed so the grid-stride remainder test
+// can size its batch past it.
+int conv3x3s2_wrw_grid_cap(int Ci) {
+  static const int cap = ft_env_int("FT_S2WRW_NBLK", 0);
+  return cap > 0 ? cap : (Ci == 16 ? 256 : 128);
+}
+
+torch::Tensor conv3x3s2_wrw(torch::Tensor dy, torch::Tensor x) {
+  TORCH_CHECK(dy.dim() == 4 && x.dim() == 4,
+              "conv3x3s2_wrw: 4D GPU tensors");
+  const int N = x.size(0), Ci = x.size(1), HI = x.size(2), WI = x.size(3);
+  const int Co = dy.size(1);
+  s2bwd_check("conv3x3s2_wrw", dy, x, Ci, Co, HI, WI);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) * 2 == HI &&
+                  dy.size(3) * 2 == WI,
+              "conv3x3s2_wrw: dy must be [N, Co, H_in/2, W_in/2]");
+  auto f32 = x.options().dtype(torch::kFloat);
+  auto dw = torch::empty(
+      {Co, Ci, 3, 3},
+      x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  TORCH_CHECK(N > 0, "conv3x3s2_wrw: empty batch");
+  const __hip_bfloat16* dyp =
+      reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr());
+  const __hip_bfloat16* xp =
+      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
+  const long tiles = (long)N * (HI / 16);          // 8 output rows each
+  const int cap = conv3x3s2_wrw_grid_cap(Ci);
+  const int nblk = (int)(tiles < cap ? tiles : cap);
+  const int Q = (Co / 16) * (Ci / 16);
+  const int RQ = nblk;                             // rows per quadrant
+  auto part = torch::empty({(long)Q * RQ, 9L * 256}, f32);
+  if (Ci == 16)
+    hipLaunchKernelGGL((conv3x3s2_wrw_k<32, 16, 32>), dim3(nblk),
+                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
+                       part.data_ptr<float>(), N, HI, RQ);
+  else
+    hipLaunchKernelGGL((conv3x3s2_wrw_k<64, 32, 16>), dim3(nblk),
+                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
+                       part.data_ptr<float>(), N, HI, RQ);
+  hipLaunchKernelGGL(conv3x3s2_wrw_final_k, dim3(Q * 72), dim3(FT_BLOCK), 0,
+                     STREAM, part.data_ptr<float>(), RQ,
+                     reinterpret_cast<__hip_bfloat16*>(dw.data_ptr()), Ci);
+  return dw;
+}
 
 
 // ==========================================================================
@@ -1795,4 +1893,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_defer", &bn_bwd_defer);
   m.def("conv3x3_bn_fwd", &conv3x3_bn_fwd);
   m.def("conv3x3s2_bn_fwd", &conv3x3s2_bn_fwd);
+  m.def("conv3x3s2_dgrad", &conv3x3s2_dgrad);
+  m.def("conv3x3s2_wrw", &conv3x3s2_wrw);
+  m.def("conv3x3s2_wrw_grid_cap", &conv3x3s2_wrw_grid_cap);
 }
