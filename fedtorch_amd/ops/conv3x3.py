@@ -9,8 +9,10 @@ Default GPU training path for the CIFAR ResNet body convs (Co == Ci,
   the `_ft_bn_part` handoff) — 5.1-6.6 us/call;
 * backward-data: conv3x3_dgrad_k (the forward's mirror) — 5.0-6.7 us
   vs MIOpen's 23-24;
-* weight gradient: MFMA wrw v2 (`hip/convwrw2.h`) for C16 where it
-  beats MIOpen-incl-wrappers (23.4 vs 33 us); MIOpen elsewhere;
+* weight gradient: MFMA wrw v2 (`hip/convwrw2.h`, main kernel + one
+  reduce/cast/scatter kernel over few, long supertile streams) for the
+  channel counts in FEDTORCH_WRW2_C; per-call figures against
+  MIOpen-incl-wrappers in profiles/wrw2_notes.md;
 * deferred BN backward (opt-in): the BN's elementwise dx pass runs
   inside the dgrad staging, handed off through a data_ptr-keyed side
   table (python tensor attrs do not survive the autograd engine's
@@ -46,16 +48,16 @@ _ENABLED = os.environ.get('FEDTORCH_MFMA_WRW', '0') == '1'
 # pass dies (its partials come out of the conv epilogue).  Default ON.
 _FWD_ENABLED = os.environ.get('FEDTORCH_MFMA_FWD', '1') == '1'
 # MFMA wrw v2 (hip/convwrw2.h): transposed-LDS staging + alignbit tap
-# shifts.  Its MAIN kernel (12.8-15.5 us/call) beats MIOpen's igemm wrw,
-# but the partial-reduce/cast/zero auxiliary kernels per call still cost
-# more than they save in-bench (148.8k vs 163.5k samples/s flagship), so
-# default OFF until the partial pipeline is dieted.  FEDTORCH_WRW2=1 to
-# enable.
+# shifts, two launches per call (main + final).  FEDTORCH_WRW2=1 forces it
+# for every body conv whatever FEDTORCH_WRW2_C says.
 _WRW2_ENABLED = os.environ.get('FEDTORCH_WRW2', '0') == '1'
-# per-shape wrw2: the v2 kernel beats MIOpen-incl-wrappers at C16
-# (23.4 vs 33 us) but not at C32/C64 — use it where it wins
+# per-shape wrw2: the channel counts whose wrw runs on the v2 kernel; the
+# default holds exactly those that beat MIOpen-incl-wrappers per call
+# (profiles/wrw2_notes.md).  Empty string = all body wrw on the library.
+_WRW2_DEFAULT_C = '16,32,64'
 _WRW2_SHAPES = set(
-    int(c) for c in os.environ.get('FEDTORCH_WRW2_C', '16').split(',')
+    int(c) for c in
+    os.environ.get('FEDTORCH_WRW2_C', _WRW2_DEFAULT_C).split(',')
     if c.strip())
 # MFMA direct conv backward-data (hip/convfwd.h conv3x3_dgrad_k): the fwd
 # kernel's mirror, 5.0-6.7 us/call vs MIOpen's 23-24.  Default ON.
@@ -137,7 +139,7 @@ class _Conv3x3BNFn(torch.autograd.Function):
                 dres if dres is not None else e)
             if not ctx.needs_input_grad[0]:
                 dx = None
-            if _WRW2_ENABLED:
+            if _WRW2_ENABLED or weight.shape[0] in _WRW2_SHAPES:
                 dw = ops._C.conv3x3_wrw2(dyc, x)
             else:
                 dw = torch.ops.aten.convolution_backward(
@@ -164,7 +166,7 @@ class _Conv3x3BNFn(torch.autograd.Function):
                 dx = torch.ops.aten.convolution_backward(
                     dy, x, weight, None, [1, 1], [1, 1], [1, 1], False,
                     [0, 0], 1, [True, False, False])[0]
-            dw = ops._C.conv3x3_wrw2(dy, x) if _WRW2_ENABLED \
+            dw = ops._C.conv3x3_wrw2(dy, x) if use_wrw2 \
                 else ops._C.conv3x3_wrw(dy, x)
         else:
             # ONE combined call (dgrad+wrw split into two was ~0.2 ms/step

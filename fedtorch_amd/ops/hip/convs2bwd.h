@@ -25,9 +25,8 @@
 // The convwrw2.h design (GEMM-K = output positions, both operands staged
 // TRANSPOSED so every fragment is one ds_read_b128, grid-stride loop over
 // supertiles, per-block fp32 partials in quadrant-local layout, no
-// atomics).  Its two-stage striped reduce + cast is replaced by ONE
-// conv3x3s2_wrw_final_k: the launcher keeps the stream count low, so there
-// are few rows to sum.  New here is the stride-2 column walk: x is staged into column-parity-split planes
+// atomics, ONE conv3x3_wrw2_final_k: the launcher keeps the stream count
+// low, so there are few rows to sum).  New here is the stride-2 column walk: x is staged into column-parity-split planes
 //   s_xT[ci][row][ even: Wo | 8 zero pad | odd: Wo ]
 // so 8 consecutive wo are contiguous for every dw: dw=1 reads the even
 // plane at wo, dw=2 the odd plane at wo, dw=0 the odd plane at wo-1 (the
@@ -345,30 +344,5 @@ __global__ void __launch_bounds__(FT_BLOCK) conv3x3s2_wrw_k(
   }
 }
 
-// part[q*RQ + r][9*16*16] fp32 -> dw bf16 [co][kh][kw][ci] in ONE kernel:
-// the launcher keeps RQ small (few, long supertile streams), so a block of
-// 32 columns (one 128 B line per row) x 8 row slices sums a quadrant's rows
-// directly; no stripe buffer, no separate cast pass.
-__global__ void __launch_bounds__(FT_BLOCK) conv3x3s2_wrw_final_k(
-    const float* __restrict__ part, int RQ, __hip_bfloat16* __restrict__ dw,
-    int CI) {
-  __shared__ float lds[8][32];
-  const int c = threadIdx.x & 31, rs = threadIdx.x >> 5;
-  const int q = blockIdx.x / 72;
-  const int lc = (blockIdx.x % 72) * 32 + c;
-  const float* p = part + (long)q * RQ * (9 * 256) + lc;
-  float s = 0.f;
-#pragma unroll 4
-  for (int r = rs; r < RQ; r += 8) s += p[(long)r * (9 * 256)];
-  lds[rs][c] = s;
-  __syncthreads();
-  if (rs == 0) {
-    s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += lds[i][c];
-    const int tap = lc / 256, mrow = (lc % 256) / 16, ncol = lc % 16;
-    const int co = (q / (CI / 16)) * 16 + mrow;
-    const int ci = (q % (CI / 16)) * 16 + ncol;
-    dw[((long)co * 9 + tap) * CI + ci] = __float2bfloat16(s);
-  }
-}
+// The partial rows are summed, cast and scattered into dw by
+// conv3x3_wrw2_final_k (convwrw2.h, same partial layout).

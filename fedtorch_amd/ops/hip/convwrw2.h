@@ -16,20 +16,28 @@
 //     by 16 bits, dw=2 is a free dword shuffle);
 //   * one supertile (128 positions; 64 = one image for W=8) is staged
 //     cooperatively per workgroup per iteration, single-buffered
-//     (stage -> barrier -> MFMAs -> barrier), overlap from 4+ resident
-//     workgroups per CU — the structure conv3x3_bn_fwd measured at
-//     5-7 us/call.
+//     (stage -> barrier -> MFMAs -> barrier), overlap from several
+//     resident workgroups per CU.
 //
-// Work split per shape (Q = (CO/16)*(CI/16) 16x16 output quadrants):
-//   C16 (Q=1):  wave w owns k-chunk w of the supertile (4 chunks x 9 taps).
-//   C32 (Q=4):  wave w owns quadrant w, loops all 4 chunks.
-//   C64 (Q=16): blocks come in groups of 4 (qg = blockIdx%4); wave w owns
-//               quadrant qg*4+w, loops the image's 2 chunks. dy/x are
-//               re-read 4x (~2 us of extra HBM traffic at these sizes).
+// Work split.  A workgroup owns COW co blocks x (CIWV*NB) ci blocks of the
+// COB x CIB grid of 16x16 output quadrants and stages only those channels
+// of dy and x.  Its 4 waves tile COW x CIWV x KS: a wave holds one co block
+// against NB ci blocks (one dy fragment feeds NB*9 MFMAs), and KS waves
+// share a quadrant by splitting the supertile's 32-position k-chunks; the
+// k-split is merged in-block through LDS (fixed order), so a workgroup
+// emits ONE partial row per quadrant it owns.  G = quadrants / owned
+// workgroups form one supertile STREAM (grid-stride over supertiles):
+//   C16: <1,1,1>  KS=4  G=1   block = the single quadrant, 4 k-chunks
+//   C32: <2,1,1>  KS=2  G=2   block = both co blocks x one ci block
+//   C64: <2,2,1>  KS=1  G=4   block = 2 x 2 quadrants, wave = quadrant
+// picked by measurement among the splits the template allows (one block
+// per stream with NB = CIB included): profiles/wrw2_notes.md.
 //
-// Partials: one row per (block, wave) in QUADRANT-LOCAL layout
-// part[q*RQ + r][9*16*16]; conv3x3_wrw2_final_k sums each quadrant's rows
-// and scatters into dw[co][kh][kw][ci] (channels_last memory order).
+// Partials are quadrant-local, part[q*RQ + stream][9*16*16] fp32 (RQ =
+// streams).  The launcher keeps the stream count low (few, long streams:
+// every stream costs one fp32 copy of dw), so ONE conv3x3_wrw2_final_k sums
+// a quadrant's rows, casts and scatters into dw[co][kh][kw][ci]
+// (channels_last memory order).  No atomics: the result is deterministic.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.h"
@@ -37,7 +45,7 @@
 
 // bf16x8 / f32x4 from convwrw.h (same TU)
 
-template <int CO, int CI, int W>
+template <int CO, int CI, int W, int COW, int CIWV, int NB>
 struct Wrw2Cfg {
   static constexpr int SPOS = (W == 8) ? 64 : 128;   // positions/supertile
   static constexpr int SR = SPOS / W;                // image rows
@@ -50,204 +58,242 @@ struct Wrw2Cfg {
   static constexpr int SX = (SXR % 16 == 8) ? SXR : ((SXR & ~15) + 8 +
                             ((SXR % 16 > 8) ? 16 : 0));
   static constexpr int SD = (SPOS % 16 == 8) ? SPOS : SPOS + 8;
-  static constexpr int Q = (CO / 16) * (CI / 16);
-  static constexpr int QG = (Q + 3) / 4;             // block-group size
+  static constexpr int COB = CO / 16, CIB = CI / 16;
+  static constexpr int Q = COB * CIB;
+  static constexpr int KS = 4 / (COW * CIWV);        // wave k-splits
+  static constexpr int BCO = COW * 16;               // staged dy channels
+  static constexpr int BCI = CIWV * NB * 16;         // staged x channels
+  static constexpr int CIG = CI / BCI;               // ci groups
+  static constexpr int G = (CO / BCO) * CIG;         // blocks per stream
+  static constexpr int SLOTS = COW * CIWV * NB;      // quadrants per block
+  static constexpr int STAGE_B = (BCO * SD + BCI * SX) * 2;
+  static constexpr int MERGE_B = (KS > 1) ? SLOTS * 36 * WAVE * 4 : 0;
+  static constexpr int LDS_B = STAGE_B > MERGE_B ? STAGE_B : MERGE_B;
+  static_assert(COW * CIWV * KS == 4 && CH % KS == 0, "wave split");
+  static_assert(CO % BCO == 0 && CI % BCI == 0, "block split");
 };
 
-template <int CO, int CI, int W>
+template <int CO, int CI, int W, int COW, int CIWV, int NB>
 __global__ void __launch_bounds__(FT_BLOCK) conv3x3_wrw2_k(
     const __hip_bfloat16* __restrict__ dy, const __hip_bfloat16* __restrict__ x,
     float* __restrict__ part, int N, int H, int RQ) {
-  using C = Wrw2Cfg<CO, CI, W>;
-  __shared__ __hip_bfloat16 s_dyT[CO * C::SD];
-  __shared__ __hip_bfloat16 s_xT[CI * C::SX];
-  __shared__ float s_merge[C::Q == 1 ? 9 * 256 : 1];  // C16 wave merge
+  using C = Wrw2Cfg<CO, CI, W, COW, CIWV, NB>;
+  // one LDS object: the staging slabs, reused by the k-split merge once
+  // the last supertile is consumed
+  __shared__ __attribute__((aligned(16))) unsigned char smem[C::LDS_B];
+  __hip_bfloat16* s_dyT = reinterpret_cast<__hip_bfloat16*>(smem);
+  __hip_bfloat16* s_xT = s_dyT + C::BCO * C::SD;
 
   const int tid = threadIdx.x;
   const int wave = tid / WAVE, lane = tid & (WAVE - 1);
   const int fm = lane & 15, kg = lane >> 4;
+  const int cow = wave % COW, ciw = (wave / COW) % CIWV;
+  const int ksp = wave / (COW * CIWV);
 
-  const int qg = (C::QG > 1) ? (blockIdx.x % C::QG) : 0;
-  const int bstream = blockIdx.x / C::QG;
-  const int nstreams = gridDim.x / C::QG;
-
-  // quadrant of this wave (C16: all waves quadrant 0)
-  const int q = (C::Q == 1) ? 0 : qg * 4 + wave;
-  const int qco = (C::Q == 1) ? 0 : (q / (CI / 16)) * 16;
-  const int qci = (C::Q == 1) ? 0 : (q % (CI / 16)) * 16;
+  const int g = (C::G > 1) ? (int)(blockIdx.x % C::G) : 0;
+  const int bstream = blockIdx.x / C::G;
+  const int nstreams = gridDim.x / C::G;
+  const int co0 = (g / C::CIG) * C::BCO;      // first dy channel staged
+  const int ci0 = (g % C::CIG) * C::BCI;      // first x channel staged
 
   // zero the x halo/padding once: body writes cover cols [1..W] of rows
   // [0..XR); everything else must read as 0 for every supertile
-  for (int e = tid; e < CI * C::SX / 8; e += FT_BLOCK)
+  for (int e = tid; e < C::BCI * C::SX / 8; e += FT_BLOCK)
     *reinterpret_cast<uint4*>(&s_xT[(long)e * 8]) = uint4{0, 0, 0, 0};
 
-  f32x4 acc[9];
+  f32x4 acc[NB][9];
 #pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = {0.f, 0.f, 0.f, 0.f};
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[b][t] = {0.f, 0.f, 0.f, 0.f};
 
   const int tiles_per_img = H / C::SR;
   const long tiles = (long)N * tiles_per_img;
   __syncthreads();
 
-  for (long tg = bstream; tg < tiles; tg += nstreams) {
+  // Staging is split into a global->register load and a register->LDS
+  // transposing store so all of a thread's loads (NDY + NX 16 B chunks) are
+  // in flight together.  Issuing the loads of supertile t+1 before t's
+  // MFMAs measured no faster (profiles/wrw2_notes.md), so it is not done.
+  constexpr int CHK_DY = C::SPOS * C::BCO / 8;
+  constexpr int CHK_X = C::XR * W * C::BCI / 8;
+  constexpr int NDY = (CHK_DY + FT_BLOCK - 1) / FT_BLOCK;
+  constexpr int NX = (CHK_X + FT_BLOCK - 1) / FT_BLOCK;
+  uint4 rdy[NDY], rx[NX];
+
+  auto load_tile = [&](long tg) {
     const int n = (int)(tg / tiles_per_img);
     const int h0 = (int)(tg % tiles_per_img) * C::SR;
-
-    // ---- stage dy transposed: [pos][co] -> s_dyT[co][pos] --------------
-    {
-      const __hip_bfloat16* dyp = dy + (((long)n * H + h0) * W) * CO;
-      constexpr int CHK = C::SPOS * CO / 8;
-      for (int e = tid; e < CHK; e += FT_BLOCK) {
-        const int pos = e * 8 / CO, c8 = (e * 8) % CO;
-        uint4 v = *reinterpret_cast<const uint4*>(dyp + (long)pos * CO + c8);
-        const __hip_bfloat16* vp =
-            reinterpret_cast<const __hip_bfloat16*>(&v);
+    const __hip_bfloat16* dyp = dy + (((long)n * H + h0) * W) * CO + co0;
+#pragma unroll
+    for (int i = 0; i < NDY; ++i) {
+      const int e = tid + i * FT_BLOCK;
+      const int pos = e * 8 / C::BCO, c8 = (e * 8) % C::BCO;
+      if (CHK_DY % FT_BLOCK == 0 || e < CHK_DY)
+        rdy[i] = *reinterpret_cast<const uint4*>(dyp + (long)pos * CO + c8);
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      const int e = tid + i * FT_BLOCK;
+      const int rowe = e * 8 / (W * C::BCI);
+      const int rem = (e * 8) % (W * C::BCI);
+      const int col = rem / C::BCI, c8 = rem % C::BCI;
+      const int hh = h0 - 1 + rowe;
+      rx[i] = uint4{0, 0, 0, 0};               // rows outside the image
+      if ((CHK_X % FT_BLOCK == 0 || e < CHK_X) && hh >= 0 && hh < H)
+        rx[i] = *reinterpret_cast<const uint4*>(
+            x + (((long)n * H + hh) * W + col) * CI + ci0 + c8);
+    }
+  };
+  // [pos][co0 + c] -> s_dyT[c][pos];  x with halo -> s_xT[c][row*XCP+col+1]
+  auto store_tile = [&]() {
+#pragma unroll
+    for (int i = 0; i < NDY; ++i) {
+      const int e = tid + i * FT_BLOCK;
+      const int pos = e * 8 / C::BCO, c8 = (e * 8) % C::BCO;
+      const __hip_bfloat16* vp =
+          reinterpret_cast<const __hip_bfloat16*>(&rdy[i]);
+      if (CHK_DY % FT_BLOCK == 0 || e < CHK_DY) {
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           s_dyT[(long)(c8 + j) * C::SD + pos] = vp[j];
       }
     }
-    // ---- stage x transposed with halo: -> s_xT[ci][row*XCP + col+1] ----
-    {
-      constexpr int CHK = C::XR * W * CI / 8;
-      for (int e = tid; e < CHK; e += FT_BLOCK) {
-        const int rowe = e * 8 / (W * CI);
-        const int rem = (e * 8) % (W * CI);
-        const int col = rem / CI, c8 = rem % CI;
-        const int hh = h0 - 1 + rowe;
-        uint4 v = {0, 0, 0, 0};
-        if (hh >= 0 && hh < H)
-          v = *reinterpret_cast<const uint4*>(
-              x + (((long)n * H + hh) * W + col) * CI + c8);
-        const __hip_bfloat16* vp =
-            reinterpret_cast<const __hip_bfloat16*>(&v);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      const int e = tid + i * FT_BLOCK;
+      const int rowe = e * 8 / (W * C::BCI);
+      const int rem = (e * 8) % (W * C::BCI);
+      const int col = rem / C::BCI, c8 = rem % C::BCI;
+      const __hip_bfloat16* vp =
+          reinterpret_cast<const __hip_bfloat16*>(&rx[i]);
+      if (CHK_X % FT_BLOCK == 0 || e < CHK_X) {
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           s_xT[(long)(c8 + j) * C::SX + rowe * C::XCP + col + 1] = vp[j];
       }
     }
+  };
+
+  for (long tg = bstream; tg < tiles; tg += nstreams) {
+    load_tile(tg);
+    store_tile();
     __syncthreads();
 
     // ---- MFMAs ----------------------------------------------------------
 #pragma unroll
-    for (int ch = 0; ch < ((C::Q == 1) ? 1 : C::CH); ++ch) {
-      const int chunk = (C::Q == 1) ? wave : ch;
+    for (int i = 0; i < C::CH / C::KS; ++i) {
+      const int chunk = ksp + i * C::KS;
       const int pb = chunk * 32 + kg * 8;       // this lane's 8 positions
       const int r0 = pb / W, w0 = pb % W;
-      bf16x8 a = *reinterpret_cast<const bf16x8*>(
-          &s_dyT[(long)(qco + fm) * C::SD + pb]);
+      const bf16x8 a = *reinterpret_cast<const bf16x8*>(
+          &s_dyT[(long)(cow * 16 + fm) * C::SD + pb]);
 #pragma unroll
-      for (int dh = 0; dh < 3; ++dh) {
-        // 16-position aligned window of this (ci, row): the dw=0/1/2
-        // fragments come out of these 8 dwords without further LDS reads
-        const __hip_bfloat16* bp =
-            &s_xT[(long)(qci + fm) * C::SX + (r0 + dh) * C::XCP + w0];
-        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-        const u32x4 lo = *reinterpret_cast<const u32x4*>(bp);
-        const u32x4 hi = *reinterpret_cast<const u32x4*>(bp + 8);
-        u32x4 f0 = lo;
-        u32x4 f1, f2 = {lo.y, lo.z, lo.w, hi.x};
-        f1.x = __builtin_amdgcn_alignbit(lo.y, lo.x, 16);
-        f1.y = __builtin_amdgcn_alignbit(lo.z, lo.y, 16);
-        f1.z = __builtin_amdgcn_alignbit(lo.w, lo.z, 16);
-        f1.w = __builtin_amdgcn_alignbit(hi.x, lo.w, 16);
-        acc[dh * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a, __builtin_bit_cast(bf16x8, f0), acc[dh * 3 + 0], 0, 0, 0);
-        acc[dh * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a, __builtin_bit_cast(bf16x8, f1), acc[dh * 3 + 1], 0, 0, 0);
-        acc[dh * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a, __builtin_bit_cast(bf16x8, f2), acc[dh * 3 + 2], 0, 0, 0);
+      for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int dh = 0; dh < 3; ++dh) {
+          // 16-position aligned window of this (ci, row): the dw=0/1/2
+          // fragments come out of these 8 dwords without further LDS reads
+          const __hip_bfloat16* bp =
+              &s_xT[(long)((ciw * NB + b) * 16 + fm) * C::SX +
+                    (r0 + dh) * C::XCP + w0];
+          typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+          const u32x4 lo = *reinterpret_cast<const u32x4*>(bp);
+          const u32x4 hi = *reinterpret_cast<const u32x4*>(bp + 8);
+          u32x4 f0 = lo;
+          u32x4 f1, f2 = {lo.y, lo.z, lo.w, hi.x};
+          f1.x = __builtin_amdgcn_alignbit(lo.y, lo.x, 16);
+          f1.y = __builtin_amdgcn_alignbit(lo.z, lo.y, 16);
+          f1.z = __builtin_amdgcn_alignbit(lo.w, lo.z, 16);
+          f1.w = __builtin_amdgcn_alignbit(hi.x, lo.w, 16);
+          acc[b][dh * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a, __builtin_bit_cast(bf16x8, f0), acc[b][dh * 3 + 0], 0, 0, 0);
+          acc[b][dh * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a, __builtin_bit_cast(bf16x8, f1), acc[b][dh * 3 + 1], 0, 0, 0);
+          acc[b][dh * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a, __builtin_bit_cast(bf16x8, f2), acc[b][dh * 3 + 2], 0, 0, 0);
+        }
       }
     }
     __syncthreads();  // slab consumed; next supertile may overwrite
   }
 
-  // ---- partial row: quadrant-local [9][16][16] ---------------------------
+  // ---- k-split merge: the KS waves of a quadrant hold k-chunk partials of
+  // the SAME outputs; waves ksp = 1..KS-1 hand theirs to ksp = 0 through
+  // the consumed slabs, one round each (fixed order), so the block emits
+  // ONE row per quadrant
+  if constexpr (C::KS > 1) {
+    float* mb = reinterpret_cast<float*>(smem);
+    const int slot0 = (cow * CIWV + ciw) * NB;
+    for (int k = 1; k < C::KS; ++k) {
+      if (k > 1) __syncthreads();             // round k-1 read out
+      if (ksp == k) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+          for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              mb[(((slot0 + b) * 9 + t) * 4 + r) * WAVE + lane] =
+                  acc[b][t][r];
+      }
+      __syncthreads();
+      if (ksp == 0) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+          for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              acc[b][t][r] +=
+                  mb[(((slot0 + b) * 9 + t) * 4 + r) * WAVE + lane];
+      }
+    }
+    if (ksp != 0) return;
+  }
+
+  // ---- partial rows: quadrant-local [9][16][16], row = stream ------------
   // D of mfma(a=dy, b=x): col = lane&15 maps the B operand's n index
   // (ci), rows map A's m (co): row = kg*4 + reg.
-  if (C::Q == 1) {
-    // the 4 waves hold CHUNK partials of the SAME quadrant: merge them
-    // through LDS so the block emits ONE row (4x less partial traffic —
-    // the reduce kernel was reading 37.7 MB/call for C16)
-    float* buf = s_merge;
-    for (int w = 1; w < 4; ++w) {
-      __syncthreads();
-      if (wave == w) {
 #pragma unroll
-        for (int t = 0; t < 9; ++t)
+  for (int b = 0; b < NB; ++b) {
+    const int q = (co0 / 16 + cow) * C::CIB + ci0 / 16 + ciw * NB + b;
+    float* pr = part + ((long)q * RQ + bstream) * (9 * 16 * 16);
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            buf[t * 256 + (kg * 4 + r) * 16 + fm] = acc[t][r];
-      }
-      __syncthreads();
-      if (wave == 0) {
+    for (int t = 0; t < 9; ++t)
 #pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            acc[t][r] += buf[t * 256 + (kg * 4 + r) * 16 + fm];
-      }
-    }
-    if (wave == 0) {
-      float* pr = part + (long)blockIdx.x * (9 * 16 * 16);
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          pr[t * 256 + (kg * 4 + r) * 16 + fm] = acc[t][r];
-    }
-    return;
-  }
-  const int rr = (C::Q == 4) ? q * RQ + (int)blockIdx.x
-                             : q * RQ + (int)bstream;
-  float* pr = part + (long)rr * (9 * 16 * 16);
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int row = kg * 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      pr[t * 256 + (row + r) * 16 + fm] = acc[t][r];
+      for (int r = 0; r < 4; ++r)
+        pr[t * 256 + (kg * 4 + r) * 16 + fm] = acc[b][t][r];
   }
 }
 
-// part[q*RQ + r][9*16*16] -> [stripe][Q*9*256] (stripe-parallel, no
-// atomics — the atomic+acc-zero version cost a fill kernel + atomic
-// round per call); conv3x3_wrw2_cast_k folds the stripes and casts.
-__global__ void __launch_bounds__(FT_BLOCK) conv3x3_wrw2_reduce_k(
-    const float* __restrict__ part, int RQ, int stripes,
-    float* __restrict__ out /* [stripes][Q*9*256] */, int Q) {
-  __shared__ float lds[4][64];
-  const int c = threadIdx.x & 63, rs = threadIdx.x >> 6;
-  const int blocks_per_q = (9 * 256) / 64 * stripes;
-  const int q = blockIdx.x / blocks_per_q;
-  const int rem = blockIdx.x % blocks_per_q;
-  const int stripe = rem % stripes;
-  const int lc = (rem / stripes) * 64 + c;
-  const int r0 = (int)((long)stripe * RQ / stripes);
-  const int r1 = (int)((long)(stripe + 1) * RQ / stripes);
+// part[q*RQ + r][9*16*16] fp32 -> dw bf16 [co][kh][kw][ci] in ONE kernel
+// (shared with the stride-2 wrw of convs2bwd.h, same partial layout): the
+// launchers keep RQ small (few, long supertile streams), so a block of CW
+// columns x 256/CW row slices sums a quadrant's rows directly; no stripe
+// buffer, no separate cast pass.  CW trades line use (32 columns = one
+// 128 B line per row) against blocks in flight (Q * 2304/CW): the small-Q
+// shapes take a narrower block to cover the chip.  Fixed summation order.
+template <int CW>
+__global__ void __launch_bounds__(FT_BLOCK) conv3x3_wrw2_final_k(
+    const float* __restrict__ part, int RQ, __hip_bfloat16* __restrict__ dw,
+    int CI) {
+  constexpr int RS = FT_BLOCK / CW;           // row slices
+  constexpr int BPQ = 9 * 256 / CW;           // blocks per quadrant
+  __shared__ float lds[RS][CW];
+  const int c = threadIdx.x % CW, rs = threadIdx.x / CW;
+  const int q = blockIdx.x / BPQ;
+  const int lc = (blockIdx.x % BPQ) * CW + c;
+  const float* p = part + (long)q * RQ * (9 * 256) + lc;
   float s = 0.f;
-  for (int r = r0 + rs; r < r1; r += 4)
-    s += part[((long)q * RQ + r) * (9 * 256) + lc];
+#pragma unroll 4
+  for (int r = rs; r < RQ; r += RS) s += p[(long)r * (9 * 256)];
   lds[rs][c] = s;
   __syncthreads();
   if (rs == 0) {
-    s = lds[0][c] + lds[1][c] + lds[2][c] + lds[3][c];
-    out[(long)stripe * (Q * 9 * 256) + (long)q * (9 * 256) + lc] = s;
-  }
-}
-
-// fold stripes + cast: [stripes][Q*9*256] fp32 -> dw bf16 [co][kh][kw][ci]
-__global__ void __launch_bounds__(FT_BLOCK) conv3x3_wrw2_cast_k(
-    const float* __restrict__ out, int stripes,
-    __hip_bfloat16* __restrict__ dw, int CO, int CI) {
-  const int total = 9 * CO * CI;
-  const int QC = ((CO / 16) * (CI / 16)) * 9 * 256;
-  for (int e = blockIdx.x * FT_BLOCK + threadIdx.x; e < total;
-       e += gridDim.x * FT_BLOCK) {
-    const int q = e / (9 * 256), lc = e % (9 * 256);
-    float s = 0.f;
-    for (int st = 0; st < stripes; ++st)
-      s += out[(long)st * QC + (long)q * (9 * 256) + lc];
+    s = 0.f;
+#pragma unroll
+    for (int i = 0; i < RS; ++i) s += lds[i][c];
     const int tap = lc / 256, mrow = (lc % 256) / 16, ncol = lc % 16;
     const int co = (q / (CI / 16)) * 16 + mrow;
     const int ci = (q % (CI / 16)) * 16 + ncol;

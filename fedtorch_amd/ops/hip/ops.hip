@@ -867,6 +867,38 @@ void cast_to_half(torch::Tensor src, torch::Tensor dst) {
 // ==========================================================================
 // MFMA wrw v2 (convwrw2.h): transposed LDS staging, alignbit tap shifts
 // ==========================================================================
+// supertile streams launched at most (a stream = the G workgroups that share
+// one grid-stride walk over the supertiles).  Every stream emits one fp32
+// copy of dw as partials (9 / 36 / 144 KB for C16 / C32 / C64), so the cap
+// trades partial traffic against busy CUs; defaults from the N=256 sweep in
+// profiles/wrw2_notes.md.  FT_WRW2_NBLK overrides (read per call, so one
+// process can sweep it).  Exposed so the grid-stride remainder test can size
+// its batch past it.
+int conv3x3_wrw2_grid_cap(int C) {
+  const int cap = ft_env_int("FT_WRW2_NBLK", 0);
+  return cap > 0 ? cap : (C == 16 ? 256 : C == 32 ? 128 : 64);
+}
+
+template <int CO, int W, int COW, int CIWV, int NB, int CW>
+static void conv3x3_wrw2_launch(const torch::Tensor& dy,
+                                const torch::Tensor& x, torch::Tensor& dw,
+                                int N, int H) {
+  using C = Wrw2Cfg<CO, CO, W, COW, CIWV, NB>;
+  const long tiles = (long)N * (H / C::SR);
+  const int cap = conv3x3_wrw2_grid_cap(CO);
+  const int RQ = (int)(tiles < cap ? tiles : cap);   // streams = rows/quadrant
+  auto part = torch::empty({(long)C::Q * RQ, 9L * 256},
+                           x.options().dtype(torch::kFloat));
+  hipLaunchKernelGGL((conv3x3_wrw2_k<CO, CO, W, COW, CIWV, NB>),
+                     dim3(RQ * C::G), dim3(FT_BLOCK), 0, STREAM,
+                     reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr()),
+                     reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
+                     part.data_ptr<float>(), N, H, RQ);
+  hipLaunchKernelGGL(conv3x3_wrw2_final_k<CW>, dim3(C::Q * (9 * 256 / CW)),
+                     dim3(FT_BLOCK), 0, STREAM, part.data_ptr<float>(), RQ,
+                     reinterpret_cast<__hip_bfloat16*>(dw.data_ptr()), CO);
+}
+
 torch::Tensor conv3x3_wrw2(torch::Tensor dy, torch::Tensor x) {
   TORCH_CHECK(dy.is_cuda() && x.is_cuda() && dy.dim() == 4 && x.dim() == 4,
               "conv3x3_wrw2: 4D GPU tensors");
@@ -883,63 +915,22 @@ torch::Tensor conv3x3_wrw2(torch::Tensor dy, torch::Tensor x) {
                                  (Co == 64 && W == 8));
   TORCH_CHECK(ok, "conv3x3_wrw2: unsupported (Co,Ci,W)=", Co, ",", Ci, ",",
               W);
-  auto f32 = x.options().dtype(torch::kFloat);
+  // a supertile is 128 positions (64 at W=8) of whole rows of ONE image
+  TORCH_CHECK(N > 0 && H > 0 && H % ((W == 8 ? 64 : 128) / W) == 0,
+              "conv3x3_wrw2: unsupported (N,H)=", N, ",", H);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W,
+              "conv3x3_wrw2: dy must be [N, Co, H, W]");
   auto dw = torch::empty(
       {Co, Ci, 3, 3},
       x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const __hip_bfloat16* dyp =
-      reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr());
-  const __hip_bfloat16* xp =
-      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
-  static const int cap = ft_env_int("FT_WRW2_NBLK", 1024);
-  int nblk, RQ, Q;
-  if (Co == 16) {
-    const long tiles = (long)N * (H / 4);        // SR=4
-    nblk = (int)(tiles < cap ? tiles : cap);
-    Q = 1;
-    RQ = nblk;                                   // waves merged in-block
-  } else if (Co == 32) {
-    const long tiles = (long)N * (H / 8);        // SR=8
-    nblk = (int)(tiles < cap ? tiles : cap);
-    Q = 4;
-    RQ = nblk;
-  } else {
-    const long tiles = (long)N;                  // SPOS = whole image
-    int streams = (int)(tiles < cap / 8 ? tiles : cap / 8);
-    nblk = streams * 4;
-    Q = 16;
-    RQ = streams;
-  }
-  auto part = torch::empty({(long)Q * RQ, 9L * 256}, f32);
+  // work split <COW, CIWV, NB> and final-kernel width per shape: see the
+  // header of convwrw2.h and the sweep in profiles/wrw2_notes.md
   if (Co == 16)
-    hipLaunchKernelGGL((conv3x3_wrw2_k<16, 16, 32>), dim3(nblk),
-                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
-                       part.data_ptr<float>(), N, H, RQ);
+    conv3x3_wrw2_launch<16, 32, 1, 1, 1, 16>(dy, x, dw, N, H);
   else if (Co == 32)
-    hipLaunchKernelGGL((conv3x3_wrw2_k<32, 32, 16>), dim3(nblk),
-                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
-                       part.data_ptr<float>(), N, H, RQ);
+    conv3x3_wrw2_launch<32, 16, 2, 1, 1, 32>(dy, x, dw, N, H);
   else
-    hipLaunchKernelGGL((conv3x3_wrw2_k<64, 64, 8>), dim3(nblk),
-                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
-                       part.data_ptr<float>(), N, H, RQ);
-  // stripes so the reduce grid covers the chip (~2048 blocks) without
-  // dropping below ~64 rows per block
-  int stripes = (int)(2048 / (Q * 36));
-  const int by_rows = RQ / 64;
-  if (stripes > by_rows) stripes = by_rows;
-  stripes = stripes < 1 ? 1 : (stripes > 16 ? 16 : stripes);
-  auto red = torch::empty({(long)stripes * Q * 9 * 256}, f32);
-  const int red_grid = Q * 36 * stripes;
-  hipLaunchKernelGGL(conv3x3_wrw2_reduce_k, dim3(red_grid), dim3(FT_BLOCK),
-                     0, STREAM, part.data_ptr<float>(), RQ, stripes,
-                     red.data_ptr<float>(), Q);
-  hipLaunchKernelGGL(conv3x3_wrw2_cast_k,
-                     dim3((9 * Co * Ci + FT_BLOCK - 1) / FT_BLOCK),
-                     dim3(FT_BLOCK), 0, STREAM, red.data_ptr<float>(),
-                     stripes,
-                     reinterpret_cast<__hip_bfloat16*>(dw.data_ptr()),
-                     Co, Ci);
+    conv3x3_wrw2_launch<64, 8, 2, 2, 1, 32>(dy, x, dw, N, H);
   return dw;
 }
 
@@ -1281,7 +1272,7 @@ torch::Tensor conv3x3s2_wrw(torch::Tensor dy, torch::Tensor x) {
     hipLaunchKernelGGL((conv3x3s2_wrw_k<64, 32, 16>), dim3(nblk),
                        dim3(FT_BLOCK), 0, STREAM, dyp, xp,
                        part.data_ptr<float>(), N, HI, RQ);
-  hipLaunchKernelGGL(conv3x3s2_wrw_final_k, dim3(Q * 72), dim3(FT_BLOCK), 0,
+  hipLaunchKernelGGL(conv3x3_wrw2_final_k<32>, dim3(Q * 72), dim3(FT_BLOCK), 0,
                      STREAM, part.data_ptr<float>(), RQ,
                      reinterpret_cast<__hip_bfloat16*>(dw.data_ptr()), Ci);
   return dw;
@@ -1888,6 +1879,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe", &mfma_probe);
   m.def("conv3x3_wrw", &conv3x3_wrw);
   m.def("conv3x3_wrw2", &conv3x3_wrw2);
+  m.def("conv3x3_wrw2_grid_cap", &conv3x3_wrw2_grid_cap);
   m.def("conv3x3_dgrad", &conv3x3_dgrad);
   m.def("conv3x3_dgrad_bn", &conv3x3_dgrad_bn);
   m.def("bn_bwd_defer", &bn_bwd_defer);
