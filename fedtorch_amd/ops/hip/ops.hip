@@ -938,11 +938,56 @@ torch::Tensor conv3x3_wrw2(torch::Tensor dy, torch::Tensor x) {
 // MFMA direct NHWC 3x3/s1/p1 conv FORWARD with fused BN prologue/epilogue
 // (convfwd.h)
 // ==========================================================================
+// argument checks shared by the convfwd.h launchers: the kernels index
+// every pointer from the activation's sizes alone, so each tensor handed
+// to them is validated here.  Optional arguments are absent when empty.
+static inline bool conv_present(const torch::Tensor& t) {
+  return t.defined() && t.numel() > 0;
+}
+
+// w: [Co, Ci, 3, 3] bf16 channels_last on the GPU (memory [Co][3][3][Ci])
+static inline void conv_check_w(const char* who, const torch::Tensor& w,
+                                int Co, int Ci) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 4, who, ": w must be 4D on GPU");
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16, who, ": bf16 only");
+  TORCH_CHECK(w.size(0) == Co && w.size(1) == Ci && w.size(2) == 3 &&
+                  w.size(3) == 3,
+              who, ": w must be [Co, Ci, 3, 3] = [", Co, ", ", Ci,
+              ", 3, 3]");
+  TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast), who,
+              ": w must be channels_last");
+}
+
+// t: bf16 channels_last GPU tensor with exactly ref's sizes
+static inline void conv_check_like(const char* who, const char* name,
+                                   const torch::Tensor& t,
+                                   const torch::Tensor& ref) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16, who, ": ",
+              name, " must be bf16 on GPU");
+  TORCH_CHECK(t.sizes() == ref.sizes() &&
+                  t.is_contiguous(at::MemoryFormat::ChannelsLast),
+              who, ": ", name, " must match ", ref.sizes(),
+              ", channels_last");
+}
+
+// ysum: [grid, Co, 2] fp32 stats partials, or empty
+static inline float* conv_check_ysum(const char* who,
+                                     const torch::Tensor& ysum, long grid,
+                                     int Co) {
+  if (!conv_present(ysum)) return nullptr;
+  TORCH_CHECK(ysum.is_cuda() && ysum.scalar_type() == torch::kFloat &&
+                  ysum.is_contiguous(),
+              who, ": ysum must be contiguous fp32 on GPU");
+  TORCH_CHECK(ysum.numel() == grid * Co * 2, who,
+              ": ysum must be [grid, Co, 2] fp32, grid=", grid);
+  return ysum.data_ptr<float>();
+}
+
 torch::Tensor conv3x3_bn_fwd(torch::Tensor x, torch::Tensor w,
                              torch::Tensor ysum, torch::Tensor in_a,
                              torch::Tensor in_b, torch::Tensor res,
                              bool relu_in) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4,
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4,
               "conv3x3_bn_fwd: 4D GPU tensors");
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
               "conv3x3_bn_fwd: channels_last only");
@@ -956,29 +1001,34 @@ torch::Tensor conv3x3_bn_fwd(torch::Tensor x, torch::Tensor w,
                                  (Co == 64 && W == 8));
   TORCH_CHECK(ok, "conv3x3_bn_fwd: unsupported (Co,Ci,W)=",
               Co, ",", Ci, ",", W);
-  TORCH_CHECK(H % 8 == 0, "conv3x3_bn_fwd: H % 8 != 0");
+  TORCH_CHECK(N > 0 && H > 0 && H % 8 == 0,
+              "conv3x3_bn_fwd: unsupported (N,H)=", N, ",", H);
+  conv_check_w("conv3x3_bn_fwd", w, Co, Ci);
   auto y = torch::empty(
       {N, Co, H, W},
       x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  float* ysp = ysum.defined() && ysum.numel() > 0
-                   ? ysum.data_ptr<float>() : nullptr;
-  if (ysp) {
-    const long grid_total =
-        (long)N * (H / 8) * (Co == 64 ? 2 : 1);
-    TORCH_CHECK(ysum.numel() == grid_total * Co * 2,
-                "conv3x3_bn_fwd: ysum must be [grid, Co, 2] fp32, grid=",
-                grid_total);
-  }
-  const float* ap = in_a.defined() && in_a.numel() > 0
-                        ? in_a.data_ptr<float>() : nullptr;
-  const float* bp = in_b.defined() && in_b.numel() > 0
-                        ? in_b.data_ptr<float>() : nullptr;
-  const __hip_bfloat16* rp =
-      res.defined() && res.numel() > 0
-          ? reinterpret_cast<const __hip_bfloat16*>(res.data_ptr())
-          : nullptr;
-  TORCH_CHECK((ap == nullptr) == (bp == nullptr),
+  float* ysp = conv_check_ysum("conv3x3_bn_fwd", ysum,
+                               (long)N * (H / 8) * (Co == 64 ? 2 : 1), Co);
+  TORCH_CHECK(conv_present(in_a) == conv_present(in_b),
               "conv3x3_bn_fwd: in_a and in_b go together");
+  const float* ap = nullptr;
+  const float* bp = nullptr;
+  if (conv_present(in_a)) {
+    TORCH_CHECK(in_a.is_cuda() && in_b.is_cuda() &&
+                    in_a.scalar_type() == torch::kFloat &&
+                    in_b.scalar_type() == torch::kFloat &&
+                    in_a.is_contiguous() && in_b.is_contiguous() &&
+                    in_a.numel() == Ci && in_b.numel() == Ci,
+                "conv3x3_bn_fwd: in_a/in_b must be fp32 [Ci] on GPU, Ci=",
+                Ci);
+    ap = in_a.data_ptr<float>();
+    bp = in_b.data_ptr<float>();
+  }
+  const __hip_bfloat16* rp = nullptr;
+  if (conv_present(res)) {
+    conv_check_like("conv3x3_bn_fwd", "res", res, x);
+    rp = reinterpret_cast<const __hip_bfloat16*>(res.data_ptr());
+  }
   const __hip_bfloat16* xp =
       reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
   const __hip_bfloat16* wp =
@@ -1022,7 +1072,7 @@ torch::Tensor conv3x3_bn_fwd(torch::Tensor x, torch::Tensor w,
 // ==========================================================================
 torch::Tensor conv3x3s2_bn_fwd(torch::Tensor x, torch::Tensor w,
                                torch::Tensor ysum) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 &&
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4 &&
                   x.is_contiguous(at::MemoryFormat::ChannelsLast),
               "conv3x3s2_bn_fwd: channels_last GPU");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
@@ -1035,17 +1085,14 @@ torch::Tensor conv3x3s2_bn_fwd(torch::Tensor x, torch::Tensor w,
                                      (Ci == 32 && WI == 16));
   TORCH_CHECK(ok, "conv3x3s2_bn_fwd: unsupported (Ci,Co,WI)=", Ci, ",",
               Co, ",", WI);
-  TORCH_CHECK(H % 8 == 0, "conv3x3s2_bn_fwd: H_out % 8 != 0");
+  TORCH_CHECK(N > 0 && HI > 0 && HI % 16 == 0,
+              "conv3x3s2_bn_fwd: unsupported (N,H_in)=", N, ",", HI);
+  conv_check_w("conv3x3s2_bn_fwd", w, Co, Ci);
   auto y = torch::empty(
       {N, Co, H, W},
       x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  float* ysp = ysum.defined() && ysum.numel() > 0
-                   ? ysum.data_ptr<float>() : nullptr;
   const int grid = N * (H / 8) * (Co / 32);
-  if (ysp)
-    TORCH_CHECK(ysum.numel() == (long)grid * Co * 2,
-                "conv3x3s2_bn_fwd: ysum must be [grid, Co, 2], grid=",
-                grid);
+  float* ysp = conv_check_ysum("conv3x3s2_bn_fwd", ysum, grid, Co);
   const __hip_bfloat16* xp =
       reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
   const __hip_bfloat16* wp =
@@ -1066,7 +1113,7 @@ torch::Tensor conv3x3s2_bn_fwd(torch::Tensor x, torch::Tensor w,
 // MFMA direct conv backward-data (convfwd.h conv3x3_dgrad_k)
 // ==========================================================================
 torch::Tensor conv3x3_dgrad(torch::Tensor dy, torch::Tensor w) {
-  TORCH_CHECK(dy.is_cuda() && w.is_cuda() && dy.dim() == 4,
+  TORCH_CHECK(dy.is_cuda() && w.is_cuda() && dy.dim() == 4 && w.dim() == 4,
               "conv3x3_dgrad: 4D GPU tensors");
   TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast),
               "conv3x3_dgrad: channels_last only");
@@ -1081,7 +1128,9 @@ torch::Tensor conv3x3_dgrad(torch::Tensor dy, torch::Tensor w) {
                                  (Co == 64 && W == 8));
   TORCH_CHECK(ok, "conv3x3_dgrad: unsupported (Co,Ci,W)=", Co, ",", Ci,
               ",", W);
-  TORCH_CHECK(H % 8 == 0, "conv3x3_dgrad: H % 8 != 0");
+  TORCH_CHECK(N > 0 && H > 0 && H % 8 == 0,
+              "conv3x3_dgrad: unsupported (N,H)=", N, ",", H);
+  conv_check_w("conv3x3_dgrad", w, Co, Ci);
   auto dx = torch::empty(
       {N, Ci, H, W},
       dy.options().memory_format(at::MemoryFormat::ChannelsLast));
@@ -1115,7 +1164,8 @@ torch::Tensor conv3x3_dgrad(torch::Tensor dy, torch::Tensor w) {
 std::vector<torch::Tensor> conv3x3_dgrad_bn(
     torch::Tensor dz, torch::Tensor w, torch::Tensor xbn, torch::Tensor z,
     torch::Tensor coefs, bool relu, torch::Tensor dres) {
-  TORCH_CHECK(dz.is_cuda() && dz.dim() == 4 &&
+  TORCH_CHECK(dz.is_cuda() && dz.dim() == 4 && w.is_cuda() &&
+                  w.dim() == 4 &&
                   dz.is_contiguous(at::MemoryFormat::ChannelsLast),
               "conv3x3_dgrad_bn: channels_last GPU dz");
   TORCH_CHECK(dz.scalar_type() == torch::kBFloat16 &&
@@ -1127,19 +1177,21 @@ std::vector<torch::Tensor> conv3x3_dgrad_bn(
   const bool ok = (Co == Ci) && ((Co == 16 && W == 32) ||
                                  (Co == 32 && W == 16) ||
                                  (Co == 64 && W == 8));
-  TORCH_CHECK(ok && H % 8 == 0, "conv3x3_dgrad_bn: unsupported shape");
+  TORCH_CHECK(ok && N > 0 && H > 0 && H % 8 == 0,
+              "conv3x3_dgrad_bn: unsupported shape");
+  conv_check_w("conv3x3_dgrad_bn", w, Co, Ci);
+  conv_check_like("conv3x3_dgrad_bn", "xbn", xbn, dz);
+  conv_check_like("conv3x3_dgrad_bn", "z", z, dz);
   TORCH_CHECK(coefs.numel() == 3 * Co && coefs.is_cuda() &&
-                  coefs.scalar_type() == torch::kFloat,
+                  coefs.scalar_type() == torch::kFloat &&
+                  coefs.is_contiguous(),
               "conv3x3_dgrad_bn: coefs must be fp32 [3, Co]");
   auto dx = torch::empty(
       {N, Ci, H, W},
       dz.options().memory_format(at::MemoryFormat::ChannelsLast));
   auto dyc = torch::empty_like(dz);
-  const bool want_dres = dres.defined() && dres.numel() > 0;
-  if (want_dres)
-    TORCH_CHECK(dres.sizes() == dz.sizes() &&
-                    dres.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv3x3_dgrad_bn: dres must match dz, channels_last");
+  const bool want_dres = conv_present(dres);
+  if (want_dres) conv_check_like("conv3x3_dgrad_bn", "dres", dres, dz);
   const __hip_bfloat16* dzp =
       reinterpret_cast<const __hip_bfloat16*>(dz.data_ptr());
   const __hip_bfloat16* wp =
@@ -1425,6 +1477,11 @@ torch::Tensor stem_conv_wrw(torch::Tensor dy, torch::Tensor x) {
   const int Co = dy.size(1);
   TORCH_CHECK(Ci == 3 && (Co == 16 || Co == 32),
               "stem_wrw: supported shapes are Ci=3, Co in {16,32}");
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W,
+              "stem_wrw: dy must be [N, Co, H, W] of x");
+  TORCH_CHECK(at::isFloatingType(x.scalar_type()) &&
+                  at::isFloatingType(dy.scalar_type()),
+              "stem_wrw: floating-point x and dy only");
   const int wn = Co * 9 * Ci;
   const int B = 1024;
   auto f32 = x.options().dtype(torch::kFloat);
