@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from fedtorch_amd.ops.batchnorm import BNReLU, BNAddReLU
+from fedtorch_amd.ops.conv3x3 import conv_bn_act
 
 _NUM_CLASSES = {'cifar10': 10, 'cifar100': 100, 'svhn': 10, 'mnist': 10,
                 'fashion_mnist': 10, 'emnist': 10, 'emnist_full': 62,
@@ -49,8 +50,10 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         identity = x if self.downsample is None else self.downsample(x)
-        out = self.bn1(self.conv1(x))
-        return self.bn2(self.conv2(out), identity)
+        # conv_bn_act == bn(conv(x)[, identity]); in eval under no_grad each
+        # pair is one fused conv+BN(+add)+ReLU launch (ops/conv3x3.py)
+        out = conv_bn_act(self.conv1, self.bn1, x)
+        return conv_bn_act(self.conv2, self.bn2, out, identity)
 
 
 class Bottleneck(nn.Module):
@@ -69,7 +72,7 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         identity = x if self.downsample is None else self.downsample(x)
         out = self.bn1(self.conv1(x))
-        out = self.bn2(self.conv2(out))
+        out = conv_bn_act(self.conv2, self.bn2, out)
         return self.bn3(self.conv3(out), identity)
 
 

@@ -4,8 +4,10 @@
 Training fwd/bwd run 2+2 hand-written streaming kernels instead of
 MIOpen's 3+3 (~40 % of ResNet-20 step kernel time, see
 profiles/r01_bench_notes.md), stats in fp32, I/O in the input dtype (bf16
-under autocast — no cast passes).  Eval mode and CPU fall back to the
-stock nn.BatchNorm2d path; state_dict layout is unchanged.
+under autocast — no cast passes).  Eval mode under no_grad runs the NHWC
+inference kernel (bn_fwd_eval, one launch incl. residual + ReLU; flag
+FEDTORCH_MFMA_EVAL in ops/conv3x3.py); eval with grad, NCHW eval and CPU
+fall back to the stock nn.BatchNorm2d path; state_dict layout is unchanged.
 """
 import torch
 import torch.nn as nn
@@ -134,6 +136,10 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
 
     def forward(self, x, res=None):
         cl = _is_cl(x)
+        if not self.training and not torch.is_grad_enabled():
+            y = self._forward_eval(x, res, cl)
+            if y is not None:
+                return y
         use_fused = (self.training and x.is_cuda and x.dim() == 4
                      and ops.hip_available() and not ops.FORCE_EAGER
                      and (not cl or _nhwc_ok(self.num_features, x.dtype)))
@@ -166,6 +172,24 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
             self.running_var if self.track_running_stats else None,
             momentum, self.eps,
             self.fuse_relu or res is not None, rc, part)
+
+    def _forward_eval(self, x, res, cl):
+        """inference under no_grad on the NHWC kernel (bnh_eval_k): one
+        launch for [relu](bn_running(x) [+ res]); None when not eligible
+        (the caller then takes the stock path).  num_batches_tracked is not
+        counted in eval."""
+        from fedtorch_amd.ops import conv3x3 as _c3
+        if not (_c3.eval_active(x) and cl
+                and _nhwc_ok(self.num_features, x.dtype)
+                and x.dtype in (torch.bfloat16, torch.float32)
+                and _c3.bn_eval_ok(self)
+                and (res is None or res.dtype == x.dtype)):
+            return None
+        rc = (res.contiguous(memory_format=torch.channels_last)
+              if res is not None else torch.empty(0, device=x.device))
+        return ops._C.bn_fwd_eval(
+            x, self.weight, self.bias, self.running_mean, self.running_var,
+            float(self.eps), self.fuse_relu or res is not None, rc)
 
     def _flush_nbt(self):
         if self._nbt_pending and self.num_batches_tracked is not None:

@@ -22,7 +22,12 @@ Default GPU training path for the CIFAR ResNet body convs (Co == Ci,
   conv3x3s2_wrw_k (column-parity-split staging) replace the one combined
   MIOpen call of _Conv3x3S2BNFn.backward — 20.7 vs 30.0 us (16->32) and
   22.5 vs 22.0 us (32->64) of device time per conv; not resolved in the
-  flagship bench, hence off by default (profiles/s2bwd_notes.md).
+  flagship bench, hence off by default (profiles/s2bwd_notes.md);
+* eval-mode forward (default, FEDTORCH_MFMA_EVAL=1): under model.eval() +
+  no_grad `conv_bn_act` runs conv + BN [+ add] + ReLU as ONE
+  conv3x3_bn_act_fwd launch (the running-stats BN folded into the conv
+  epilogue) — ResNet-20 forward 0.43-0.52 vs 2.60 ms at N=256
+  (profiles/eval_notes.md).
 
 Anything else falls back to stock F.conv2d autograd.  Per-call evidence:
 profiles/r02_bench_notes.md; kernel details: hip/README.md.
@@ -80,6 +85,13 @@ _BNDEFER_ENABLED = os.environ.get('FEDTORCH_BN_DEFER', '0') == '1'
 # (FEDTORCH_MFMA_S2_BWD=1); per-call and in-bench figures in
 # profiles/s2bwd_notes.md.
 _S2BWD_ENABLED = os.environ.get('FEDTORCH_MFMA_S2_BWD', '0') == '1'
+# Eval-mode forward on the kernel pack (model.eval() + no_grad): every
+# conv3x3 + BN [+ add] + ReLU group is ONE conv3x3_bn_act_fwd launch (the
+# running-stats BN is a per-channel affine on the conv accumulators,
+# hip/convfwd.h), the stem / downsample BNs run bn_fwd_eval
+# (hip/batchnorm.h).  Default and figures: profiles/eval_notes.md.
+_EVAL_DEFAULT = '1'
+_EVAL_ENABLED = os.environ.get('FEDTORCH_MFMA_EVAL', _EVAL_DEFAULT) == '1'
 _BNBWD_TAGS = {}
 
 
@@ -368,3 +380,70 @@ class NhwcConv3x3(nn.Conv2d):
             return F.conv2d(x, w, self.bias, self.stride, self.padding,
                             self.dilation, self.groups)
         return _Conv3x3Fn.apply(x, w)
+
+
+def eval_active(x):
+    """the eval-mode kernel path applies to this call (the module's own
+    `not self.training` is checked by the caller, first)"""
+    return (_EVAL_ENABLED and not torch.is_grad_enabled() and x.is_cuda
+            and ops.hip_available() and not ops.FORCE_EAGER)
+
+
+def bn_eval_ok(bn):
+    """an eval BN the kernels can fold: affine + tracked fp32 buffers"""
+    return (bn.affine and bn.track_running_stats
+            and bn.running_mean is not None and bn.running_var is not None
+            and bn.weight is not None and bn.bias is not None
+            and bn.weight.dtype == torch.float32
+            and bn.running_mean.dtype == torch.float32)
+
+
+def _eval_conv_stride(conv, x):
+    """1 / 2 when `conv` on `x` is a shape the MFMA forward kernels cover
+    (the training path's shape, dtype and layout conditions), else 0"""
+    if not (x.dim() == 4 and conv.bias is None and conv.padding == (1, 1)
+            and x.dtype == torch.bfloat16
+            and x.is_contiguous(memory_format=_CL)):
+        return 0
+    if (conv.stride == (1, 1) and conv.in_channels == conv.out_channels
+            and (conv.out_channels, x.shape[3]) in _SHAPES
+            and x.shape[2] % 8 == 0):
+        return 1
+    if (conv.stride == (2, 2)
+            and conv.out_channels == 2 * conv.in_channels
+            and (conv.in_channels, x.shape[3]) in ((16, 32), (32, 16))
+            and x.shape[2] % 16 == 0):
+        return 2
+    return 0
+
+
+def conv_bn_act(conv, bn_mod, x, res=None):
+    """``bn_mod(conv(x))`` / ``bn_mod(conv(x), res)`` for a conv followed by
+    a BNReLU / BNAddReLU.  In eval under no_grad, with an eligible
+    NhwcConv3x3 and a FusedBatchNorm2d inside `bn_mod`, the whole group is
+    one conv3x3_bn_act_fwd launch; anything else is exactly the two module
+    calls."""
+    if _EVAL_ENABLED and not conv.training and not bn_mod.training \
+            and eval_active(x):
+        from fedtorch_amd.ops.batchnorm import (
+            BNAddReLU, BNReLU, FusedBatchNorm2d)
+        bn = getattr(bn_mod, 'bn', None)
+        has_res = isinstance(bn_mod, BNAddReLU)
+        stride = 0
+        if (isinstance(conv, NhwcConv3x3) and isinstance(bn, FusedBatchNorm2d)
+                and (has_res or isinstance(bn_mod, BNReLU))
+                and has_res == (res is not None) and bn_eval_ok(bn)
+                and (res is None or res.dtype == torch.bfloat16)):
+            stride = _eval_conv_stride(conv, x)
+        if stride:
+            w = conv.weight
+            wb = w if w.dtype == torch.bfloat16 else \
+                w.bfloat16().contiguous(memory_format=_CL)
+            if wb.is_contiguous(memory_format=_CL):
+                rc = res.contiguous(memory_format=_CL) if has_res \
+                    else _empty(x.device)
+                return ops._C.conv3x3_bn_act_fwd(
+                    x, wb, bn.weight, bn.bias, bn.running_mean,
+                    bn.running_var, float(bn.eps), True, rc, stride)
+    y = conv(x)
+    return bn_mod(y) if res is None else bn_mod(y, res)

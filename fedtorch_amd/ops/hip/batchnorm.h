@@ -377,6 +377,63 @@ __global__ void bnh_norm_k(const T* __restrict__ x, T* __restrict__ y,
   }
 }
 
+// ---- inference (running statistics) ---------------------------------------
+// per-channel fold of an eval-mode BN into y = a*x + b.  IEEE sqrt and
+// divide (not rsqrtf): with eps = 0 and var a power of 4 the scale is exact,
+// which the exact-integer tests rely on.  Shared with the conv inference
+// epilogue (convfwd.h) so both kernels fold identically.
+__device__ __forceinline__ void bn_eval_fold(
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ running_mean,
+    const float* __restrict__ running_var, float eps, int c, float* a,
+    float* b) {
+  const float inv = 1.0f / sqrtf(running_var[c] + eps);
+  const float sc = gamma[c] * inv;
+  *a = sc;
+  *b = beta[c] - running_mean[c] * sc;
+}
+
+// y = [relu](a[c]*x + b[c] [+ res]) with (a, b) folded per block into LDS
+// from the four fp32 [C] vectors; same task split as bnh_norm_k's streaming
+// loop (one 16 B vector = VN channels of one row per thread-iteration).
+// HAS_RES is compile-time so the residual load is not branched around.
+template <typename T, typename VT, int VN, bool HAS_RES>
+__global__ void __launch_bounds__(FT_BLOCK) bnh_eval_k(
+    const T* __restrict__ x, T* __restrict__ y,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ running_mean,
+    const float* __restrict__ running_var, const T* __restrict__ res,
+    long NI, long C, int lgc, float eps, int relu) {
+  __shared__ float lsc[256], lsh[256];
+  if (threadIdx.x < C)
+    bn_eval_fold(gamma, beta, running_mean, running_var, eps, threadIdx.x,
+                 &lsc[threadIdx.x], &lsh[threadIdx.x]);
+  __syncthreads();
+  const int cgc = 1 << lgc;
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned cg = t & (cgc - 1);
+  const unsigned rstride = (gridDim.x * blockDim.x) >> lgc;
+  float sc[VN], sh[VN];
+#pragma unroll
+  for (int j = 0; j < VN; ++j) {
+    sc[j] = lsc[cg * VN + j];
+    sh[j] = lsh[cg * VN + j];
+  }
+  for (long r = t >> lgc; r < NI; r += rstride) {
+    const long base = r * C + cg * VN;
+    VT v = *reinterpret_cast<const VT*>(x + base);
+    VT rv = v;
+    if (HAS_RES) rv = *reinterpret_cast<const VT*>(res + base);
+#pragma unroll
+    for (int j = 0; j < VN; ++j) {
+      float f = fmaf((float)v.d[j], sc[j], sh[j]);
+      if (HAS_RES) f += (float)rv.d[j];
+      v.d[j] = (T)(relu ? fmaxf(f, 0.f) : f);
+    }
+    *reinterpret_cast<VT*>(y + base) = v;
+  }
+}
+
 template <typename T, typename VT, int VN>
 __global__ void bnh_bwd_stats_k(const T* __restrict__ dy,
                                 const T* __restrict__ x,

@@ -29,11 +29,18 @@
 #include "common.h"
 #include <hip/hip_bf16.h>
 
-// bf16x8 / f32x4 come from convwrw.h (same TU)
+// bf16x8 / f32x4 come from convwrw.h, bn_eval_fold from batchnorm.h (same
+// TU)
 
+// The kernel body is shared by two __global__ entry points below:
+//   EVAL = false  conv3x3_bn_fwd_k      (training: stats-partials epilogue)
+//   EVAL = true   conv3x3_bn_act_fwd_k  (inference: the BN's running-stats
+//                 affine [+ residual] [+ ReLU] applied to the accumulators)
+// With EVAL, FUSE_IN is false and HAS_RES / res / relu_in describe the
+// OUTPUT side: res is [N, H, W, CO] and relu_in is the output ReLU.
 template <int CI, int CO, int CO_TILE, int W, bool FUSE_IN, bool HAS_RES,
-          int S = 1>
-__global__ void __launch_bounds__(FT_BLOCK) conv3x3_bn_fwd_k(
+          int S, bool EVAL>
+__device__ __forceinline__ void conv3x3_fwd_body(
     const __hip_bfloat16* __restrict__ x,   // [N, H*S, W*S, CI]
     const __hip_bfloat16* __restrict__ w,   // [CO, 3, 3, CI]
     __hip_bfloat16* __restrict__ y,         // [N, H, W, CO]  (H, W = OUT)
@@ -41,7 +48,12 @@ __global__ void __launch_bounds__(FT_BLOCK) conv3x3_bn_fwd_k(
     const float* __restrict__ in_a,         // [CI] scale or null
     const float* __restrict__ in_b,         // [CI] shift
     const __hip_bfloat16* __restrict__ res, // residual or null
-    int N, int H, int relu_in) {
+    const float* __restrict__ bn_gamma,     // EVAL: [CO] BN weight
+    const float* __restrict__ bn_beta,      // EVAL: [CO] BN bias
+    const float* __restrict__ bn_mean,      // EVAL: [CO] running_mean
+    const float* __restrict__ bn_var,       // EVAL: [CO] running_var
+    float bn_eps, int N, int H, int relu_in) {
+  static_assert(!EVAL || !FUSE_IN, "the inference epilogue takes raw x");
   constexpr int R = 8;                    // output rows per workgroup
   constexpr int WI = W * S;               // input row width
   constexpr int KTOT = 9 * CI;
@@ -76,6 +88,12 @@ __global__ void __launch_bounds__(FT_BLOCK) conv3x3_bn_fwd_k(
     sa[tid] = in_a[tid];
     sb[tid] = in_b[tid];
   }
+  // EVAL: fold this workgroup's CO_TILE channels of the BN (running stats)
+  // into (scale, shift); read after the staging barriers below
+  __shared__ float ea[EVAL ? CO_TILE : 1], eb[EVAL ? CO_TILE : 1];
+  if (EVAL && tid < CO_TILE)
+    bn_eval_fold(bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, co0 + tid,
+                 &ea[tid], &eb[tid]);
 
   // ---- stage weights: bw[k/8][co][j] = w[co0+co][tap][ci], k=tap*CI+ci --
   for (int e = tid; e < K8 * CO_TILE; e += FT_BLOCK) {
@@ -184,8 +202,31 @@ __global__ void __launch_bounds__(FT_BLOCK) conv3x3_bn_fwd_k(
     }
   }
 
-  // ---- epilogue: store y + per-channel sum/sumsq ------------------------
   // D: col(channel) = fm, row(pixel-in-tile) = kg*4 + reg
+  if (EVAL) {
+    // ---- inference epilogue: y = [relu](a*acc + b [+ res]) --------------
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt) {
+      const int ptile = (wave * MTW + mt) * 16;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const float a = ea[nt * 16 + fm], b = eb[nt * 16 + fm];
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const int p = ptile + kg * 4 + r4;   // pixel in WG tile
+          const int hh = h0 + p / W, cc = p % W;
+          const long o =
+              (((long)n * H + hh) * W + cc) * CO + co0 + nt * 16 + fm;
+          float v = fmaf(a, acc[mt][nt][r4], b);
+          if (HAS_RES) v += (float)res[o];
+          if (relu_in) v = fmaxf(v, 0.f);
+          y[o] = (__hip_bfloat16)v;
+        }
+      }
+    }
+    return;
+  }
+  // ---- epilogue: store y + per-channel sum/sumsq ------------------------
   float s[NT], ss[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) { s[nt] = 0.f; ss[nt] = 0.f; }
@@ -243,6 +284,45 @@ __global__ void __launch_bounds__(FT_BLOCK) conv3x3_bn_fwd_k(
       prow[c0 * 2 + 1] = tss;
     }
   }
+}
+
+template <int CI, int CO, int CO_TILE, int W, bool FUSE_IN, bool HAS_RES,
+          int S = 1>
+__global__ void __launch_bounds__(FT_BLOCK) conv3x3_bn_fwd_k(
+    const __hip_bfloat16* __restrict__ x,   // [N, H*S, W*S, CI]
+    const __hip_bfloat16* __restrict__ w,   // [CO, 3, 3, CI]
+    __hip_bfloat16* __restrict__ y,         // [N, H, W, CO]  (H, W = OUT)
+    float* __restrict__ ysum,               // [2*CO] (sum, sumsq) or null
+    const float* __restrict__ in_a,         // [CI] scale or null
+    const float* __restrict__ in_b,         // [CI] shift
+    const __hip_bfloat16* __restrict__ res, // residual or null
+    int N, int H, int relu_in) {
+  conv3x3_fwd_body<CI, CO, CO_TILE, W, FUSE_IN, HAS_RES, S, false>(
+      x, w, y, ysum, in_a, in_b, res, nullptr, nullptr, nullptr, nullptr,
+      0.f, N, H, relu_in);
+}
+
+// Inference: y = [relu](bn_running(conv3x3(x, w)) [+ res]) in ONE launch.
+// The BN statistics are the running buffers, known before the conv starts,
+// so the whole BN(+add)(+ReLU) is a per-channel affine on the accumulators;
+// each workgroup folds its CO_TILE channels itself (no side kernel, no
+// host arithmetic: the weights change every round, a cached fold goes
+// stale).  HAS_RES is compile-time for the reason given in the staging
+// loop; relu guards no load and is a runtime argument.
+template <int CI, int CO, int CO_TILE, int W, bool HAS_RES, int S = 1>
+__global__ void __launch_bounds__(FT_BLOCK) conv3x3_bn_act_fwd_k(
+    const __hip_bfloat16* __restrict__ x,   // [N, H*S, W*S, CI]
+    const __hip_bfloat16* __restrict__ w,   // [CO, 3, 3, CI]
+    __hip_bfloat16* __restrict__ y,         // [N, H, W, CO]  (H, W = OUT)
+    const float* __restrict__ gamma,        // [CO]
+    const float* __restrict__ beta,         // [CO]
+    const float* __restrict__ running_mean, // [CO]
+    const float* __restrict__ running_var,  // [CO]
+    const __hip_bfloat16* __restrict__ res, // [N, H, W, CO] or null
+    float eps, int N, int H, int relu) {
+  conv3x3_fwd_body<CI, CO, CO_TILE, W, false, HAS_RES, S, true>(
+      x, w, y, nullptr, nullptr, nullptr, res, gamma, beta, running_mean,
+      running_var, eps, N, H, relu);
 }
 
 

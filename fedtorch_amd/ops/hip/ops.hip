@@ -1110,6 +1110,96 @@ torch::Tensor conv3x3s2_bn_fwd(torch::Tensor x, torch::Tensor w,
 }
 
 // ==========================================================================
+// MFMA conv fwd with the INFERENCE epilogue (convfwd.h
+// conv3x3_bn_act_fwd_k): y = [relu](bn_running(conv3x3(x, w)) [+ res]),
+// stride 1 (body shapes) or 2 (transitions), one launch
+// ==========================================================================
+// t: contiguous fp32 [n] on the GPU
+static inline const float* conv_check_vec(const char* who, const char* name,
+                                          const torch::Tensor& t, int n) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat, who, ": ",
+              name, " must be fp32 on GPU");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == n && t.is_contiguous(), who, ": ",
+              name, " must be contiguous [Co] = [", n, "]");
+  return t.data_ptr<float>();
+}
+
+torch::Tensor conv3x3_bn_act_fwd(torch::Tensor x, torch::Tensor w,
+                                 torch::Tensor gamma, torch::Tensor beta,
+                                 torch::Tensor running_mean,
+                                 torch::Tensor running_var, double eps,
+                                 bool relu, torch::Tensor res, long stride) {
+  const char* who = "conv3x3_bn_act_fwd";
+  TORCH_CHECK(stride == 1 || stride == 2, who, ": stride must be 1 or 2, got ",
+              stride);
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4, who, ": x must be 4D on GPU");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, who, ": bf16 only");
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), who,
+              ": channels_last only");
+  TORCH_CHECK(w.dim() == 4, who, ": w must be 4D");
+  const int N = x.size(0), Ci = x.size(1), HI = x.size(2), WI = x.size(3);
+  const int Co = w.size(0);
+  const int S = (int)stride;
+  bool ok;
+  if (S == 1)
+    ok = (Co == Ci) && ((Co == 16 && WI == 32) || (Co == 32 && WI == 16) ||
+                        (Co == 64 && WI == 8));
+  else
+    ok = (Co == 2 * Ci) && ((Ci == 16 && WI == 32) || (Ci == 32 && WI == 16));
+  TORCH_CHECK(ok, who, ": unsupported (Ci,Co,W)=", Ci, ",", Co, ",", WI,
+              " at stride ", S);
+  TORCH_CHECK(N > 0 && HI > 0 && HI % (8 * S) == 0, who,
+              ": unsupported (N,H)=", N, ",", HI, " at stride ", S);
+  conv_check_w(who, w, Co, Ci);
+  const float* gp = conv_check_vec(who, "gamma", gamma, Co);
+  const float* bp = conv_check_vec(who, "beta", beta, Co);
+  const float* mp = conv_check_vec(who, "running_mean", running_mean, Co);
+  const float* vp = conv_check_vec(who, "running_var", running_var, Co);
+  const int H = HI / S, W = WI / S;
+  auto y = torch::empty(
+      {N, Co, H, W},
+      x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const __hip_bfloat16* rp = nullptr;
+  if (conv_present(res)) {
+    conv_check_like(who, "res", res, y);   // the OUTPUT shape
+    rp = reinterpret_cast<const __hip_bfloat16*>(res.data_ptr());
+  }
+  const __hip_bfloat16* xp =
+      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
+  const __hip_bfloat16* wp =
+      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
+  __hip_bfloat16* yp = reinterpret_cast<__hip_bfloat16*>(y.data_ptr());
+  TORCH_CHECK((long)N * (H / 8) * 2 < (1L << 31), who, ": N too large");
+#define FT_CONV_EVAL_LAUNCH(CI_, CO_, COT_, W_, S_)                        \
+  {                                                                        \
+    const int grid = N * (H / 8) * (CO_ / COT_);                           \
+    if (rp != nullptr)                                                     \
+      hipLaunchKernelGGL(                                                  \
+          (conv3x3_bn_act_fwd_k<CI_, CO_, COT_, W_, true, S_>), dim3(grid), \
+          dim3(FT_BLOCK), 0, STREAM, xp, wp, yp, gp, bp, mp, vp, rp,       \
+          (float)eps, N, H, relu ? 1 : 0);                                 \
+    else                                                                   \
+      hipLaunchKernelGGL(                                                  \
+          (conv3x3_bn_act_fwd_k<CI_, CO_, COT_, W_, false, S_>),           \
+          dim3(grid), dim3(FT_BLOCK), 0, STREAM, xp, wp, yp, gp, bp, mp,   \
+          vp, rp, (float)eps, N, H, relu ? 1 : 0);                         \
+  }
+  if (S == 1 && Co == 16) {
+    FT_CONV_EVAL_LAUNCH(16, 16, 16, 32, 1)
+  } else if (S == 1 && Co == 32) {
+    FT_CONV_EVAL_LAUNCH(32, 32, 32, 16, 1)
+  } else if (S == 1) {
+    FT_CONV_EVAL_LAUNCH(64, 64, 32, 8, 1)
+  } else if (Ci == 16) {
+    FT_CONV_EVAL_LAUNCH(16, 32, 32, 16, 2)
+  } else {
+    FT_CONV_EVAL_LAUNCH(32, 64, 32, 8, 2)
+  }
+#undef FT_CONV_EVAL_LAUNCH
+  return y;
+}
+
+// ==========================================================================
 // MFMA direct conv backward-data (convfwd.h conv3x3_dgrad_k)
 // ==========================================================================
 torch::Tensor conv3x3_dgrad(torch::Tensor dy, torch::Tensor w) {
@@ -1747,6 +1837,69 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor weight,
   return {y, save_mean, save_ivar, mask};
 }
 
+// NHWC inference BatchNorm: y = [relu](bn_running(x) [+ res]), one streaming
+// launch (batchnorm.h bnh_eval_k); bf16 or fp32, channels_last only.
+template <typename T>
+static void bn_fwd_eval_launch(const torch::Tensor& x, torch::Tensor& y,
+                               const float* gp, const float* bp,
+                               const float* mp, const float* vp,
+                               const torch::Tensor& res, long NI, long C,
+                               float eps, bool relu) {
+  constexpr int VN = BnVec<T>::N;
+  using V = typename BnVec<T>::V;
+  TORCH_CHECK(bnh_ok(C, VN), "bn_fwd_eval: unsupported C=", C);
+  const int lgc = bnh_lgc(C, VN);
+  const long tasks = NI << lgc;
+  const T* xp = reinterpret_cast<const T*>(x.data_ptr());
+  T* yp = reinterpret_cast<T*>(y.data_ptr());
+  if (res.numel())
+    hipLaunchKernelGGL((bnh_eval_k<T, V, VN, true>), dim3(bnh_ew_grid(tasks)),
+                       dim3(FT_BLOCK), 0, STREAM, xp, yp, gp, bp, mp, vp,
+                       reinterpret_cast<const T*>(res.data_ptr()), NI, C,
+                       lgc, eps, relu ? 1 : 0);
+  else
+    hipLaunchKernelGGL((bnh_eval_k<T, V, VN, false>),
+                       dim3(bnh_ew_grid(tasks)), dim3(FT_BLOCK), 0, STREAM,
+                       xp, yp, gp, bp, mp, vp, (const T*)nullptr, NI, C, lgc,
+                       eps, relu ? 1 : 0);
+}
+
+torch::Tensor bn_fwd_eval(torch::Tensor x, torch::Tensor gamma,
+                          torch::Tensor beta, torch::Tensor running_mean,
+                          torch::Tensor running_var, double eps, bool relu,
+                          torch::Tensor res) {
+  const char* who = "bn_fwd_eval";
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4, who, ": x must be 4D on GPU");
+  // (a 1x1 map is channels_last AND plainly contiguous: same memory)
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), who,
+              ": channels_last only");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 ||
+                  x.scalar_type() == torch::kFloat,
+              who, ": bf16 or fp32 only");
+  const long N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(N * HW > 0, who, ": empty input");
+  const float* gp = conv_check_vec(who, "gamma", gamma, (int)C);
+  const float* bp = conv_check_vec(who, "beta", beta, (int)C);
+  const float* mp = conv_check_vec(who, "running_mean", running_mean, (int)C);
+  const float* vp = conv_check_vec(who, "running_var", running_var, (int)C);
+  if (conv_present(res)) {
+    TORCH_CHECK(res.is_cuda() && res.scalar_type() == x.scalar_type() &&
+                    res.sizes() == x.sizes() &&
+                    res.is_contiguous(at::MemoryFormat::ChannelsLast),
+                who, ": res must match x (", x.sizes(),
+                ", same dtype, channels_last)");
+  }
+  auto y = torch::empty(
+      x.sizes(), x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  if (x.scalar_type() == torch::kBFloat16)
+    bn_fwd_eval_launch<__hip_bfloat16>(x, y, gp, bp, mp, vp, res, N * HW, C,
+                                       (float)eps, relu);
+  else
+    bn_fwd_eval_launch<float>(x, y, gp, bp, mp, vp, res, N * HW, C,
+                              (float)eps, relu);
+  return y;
+}
+
 std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, torch::Tensor x,
                                   torch::Tensor y, torch::Tensor mask,
                                   torch::Tensor save_mean,
@@ -1942,6 +2095,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_defer", &bn_bwd_defer);
   m.def("conv3x3_bn_fwd", &conv3x3_bn_fwd);
   m.def("conv3x3s2_bn_fwd", &conv3x3s2_bn_fwd);
+  m.def("conv3x3_bn_act_fwd", &conv3x3_bn_act_fwd);
+  m.def("bn_fwd_eval", &bn_fwd_eval);
   m.def("conv3x3s2_dgrad", &conv3x3s2_dgrad);
   m.def("conv3x3s2_wrw", &conv3x3s2_wrw);
   m.def("conv3x3s2_wrw_grid_cap", &conv3x3s2_wrw_grid_cap);
