@@ -1658,6 +1658,64 @@ static inline int bnh_ew_grid(long tasks) {
   return (int)(b < 1 ? 1 : b);
 }
 
+// ---- launcher argument checks (all run before any allocation/launch) ----
+// 16 B vector width of the NHWC kernels for x's dtype; 0 = unsupported
+static inline int bn_vn(const torch::Tensor& x) {
+  switch (x.scalar_type()) {
+    case torch::kBFloat16: return 8;
+    case torch::kFloat: return 4;
+    case torch::kDouble: return 2;
+    default: return 0;
+  }
+}
+
+// x: 4D on the GPU, bf16/fp32/fp64, N*HW < 2^31 (u32 row/element indices)
+static inline void bn_check_x(const char* who, const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4, who, ": x must be 4D on GPU");
+  TORCH_CHECK(bn_vn(x) != 0, who, ": x must be bf16, fp32 or fp64");
+  TORCH_CHECK(x.size(0) * x.size(2) * x.size(3) < (1L << 31), who,
+              ": N*HW must fit in int32");
+}
+
+// activation-shaped operand: same dtype, sizes and memory layout as x
+static inline void bn_check_like(const char* who, const char* name,
+                                 const torch::Tensor& t,
+                                 const torch::Tensor& x, bool nhwc) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == x.scalar_type(), who, ": ",
+              name, " must match x (same dtype, on GPU)");
+  TORCH_CHECK(t.dim() == 4 && t.sizes() == x.sizes() &&
+                  (nhwc ? t.is_contiguous(at::MemoryFormat::ChannelsLast)
+                        : t.is_contiguous()),
+              who, ": ", name, " must match x (", x.sizes(), ", ",
+              nhwc ? "channels_last" : "contiguous", ")");
+}
+
+// per-channel fp32 vector of length C; an empty tensor means "absent"
+static inline const float* bn_check_vec(const char* who, const char* name,
+                                        const torch::Tensor& t, long C,
+                                        bool optional) {
+  if (!conv_present(t)) {
+    TORCH_CHECK(optional, who, ": ", name, " must be fp32 [C] = [", C, "]");
+    return nullptr;
+  }
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat, who, ": ",
+              name, " must be fp32 on GPU");
+  TORCH_CHECK(t.numel() == C && t.is_contiguous(), who, ": ", name,
+              " must be contiguous [C] = [", C, "]");
+  return t.data_ptr<float>();
+}
+
+// running_mean / running_var go together
+static inline void bn_check_running(const char* who,
+                                    const torch::Tensor& running_mean,
+                                    const torch::Tensor& running_var,
+                                    long C) {
+  TORCH_CHECK(conv_present(running_mean) == conv_present(running_var), who,
+              ": running_mean and running_var go together");
+  bn_check_vec(who, "running_mean", running_mean, C, true);
+  bn_check_vec(who, "running_var", running_var, C, true);
+}
+
 // collapse [G, C, 2] stats partials to [B2, C, 2]: bnh_norm_k's
 // per-block finalize re-reads ALL partial rows in EVERY normalize block
 // (B=1024 conv-epilogue rows measured 21 us/norm vs 7.9 at B~64).
@@ -1670,6 +1728,16 @@ __global__ void __launch_bounds__(FT_BLOCK) part_reduce_k(
   __shared__ float lds[FT_BLOCK];
   const long r0 = (long)blockIdx.x * G / B2;
   const long r1 = (long)(blockIdx.x + 1) * G / B2;
+  if (cols > FT_BLOCK) {
+    // more columns than threads (C > 128): no row-parallel split, each
+    // thread walks columns c, c + FT_BLOCK, ... serially over the rows
+    for (int cc = threadIdx.x; cc < cols; cc += FT_BLOCK) {
+      float a = 0.f;
+      for (long r = r0; r < r1; ++r) a += part[r * cols + cc];
+      out[(long)blockIdx.x * cols + cc] = a;
+    }
+    return;
+  }
   const int rp = FT_BLOCK / cols;            // row-parallel factor
   const int c = threadIdx.x % cols, p = threadIdx.x / cols;
   float s = 0.f;
@@ -1690,15 +1758,23 @@ std::vector<torch::Tensor> bn_fwd_train_part(
     torch::Tensor x, torch::Tensor part, torch::Tensor weight,
     torch::Tensor bias, torch::Tensor running_mean, torch::Tensor running_var,
     double eps, double momentum, bool relu, torch::Tensor res) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4, "bn_fwd_train_part: 4D GPU");
+  const char* who = "bn_fwd_train_part";
+  bn_check_x(who, x);
   const bool nhwc =
       x.is_contiguous(at::MemoryFormat::ChannelsLast) && !x.is_contiguous();
   TORCH_CHECK(nhwc, "bn_fwd_train_part: channels_last only");
   long N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(bnh_ok(C, bn_vn(x)), "bn_fwd_train_part: unsupported C=", C);
   TORCH_CHECK(part.is_cuda() && part.dim() == 3 && part.size(1) == C &&
                   part.size(2) == 2 &&
                   part.scalar_type() == torch::kFloat,
               "bn_fwd_train_part: part must be [B, C, 2] fp32");
+  TORCH_CHECK(part.size(0) >= 1 && part.is_contiguous(),
+              "bn_fwd_train_part: part must be contiguous with B >= 1 rows");
+  bn_check_vec(who, "weight", weight, C, true);
+  bn_check_vec(who, "bias", bias, C, true);
+  bn_check_running(who, running_mean, running_var, C);
+  if (conv_present(res)) bn_check_like(who, "res", res, x, true);
   auto f32 = x.options().dtype(torch::kFloat);
   auto save_mean = torch::empty({C}, f32);
   auto save_ivar = torch::empty({C}, f32);
@@ -1748,12 +1824,18 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor weight,
                                         torch::Tensor running_var,
                                         double eps, double momentum,
                                         bool relu, torch::Tensor res) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4, "bn_fwd_train expects 4D GPU");
+  const char* who = "bn_fwd_train";
+  bn_check_x(who, x);
   const bool nhwc =
       x.is_contiguous(at::MemoryFormat::ChannelsLast) && !x.is_contiguous();
   TORCH_CHECK(nhwc || x.is_contiguous(), "bn_fwd_train: x not contiguous");
   long N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
-  TORCH_CHECK(N * HW < (1L << 31), "bn_fwd_train: N*HW must fit in int32");
+  TORCH_CHECK(!nhwc || bnh_ok(C, bn_vn(x)),
+              "bn_fwd_train NHWC: unsupported C=", C);
+  bn_check_vec(who, "weight", weight, C, true);
+  bn_check_vec(who, "bias", bias, C, true);
+  bn_check_running(who, running_mean, running_var, C);
+  if (conv_present(res)) bn_check_like(who, "res", res, x, nhwc);
   auto f32 = x.options().dtype(torch::kFloat);
   auto save_mean = torch::empty({C}, f32);
   auto save_ivar = torch::empty({C}, f32);
@@ -1906,11 +1988,31 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, torch::Tensor x,
                                   torch::Tensor save_ivar,
                                   torch::Tensor weight, bool relu,
                                   bool has_res) {
-  TORCH_CHECK(x.is_cuda() && dy.is_cuda(), "bn_bwd expects GPU tensors");
+  const char* who = "bn_bwd";
+  bn_check_x(who, x);
   const bool nhwc =
       x.is_contiguous(at::MemoryFormat::ChannelsLast) && !x.is_contiguous();
+  TORCH_CHECK(nhwc || x.is_contiguous(), "bn_bwd: x/dy must be contiguous");
   long N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
-  TORCH_CHECK(N * HW < (1L << 31), "bn_bwd: N*HW must fit in int32");
+  TORCH_CHECK(!nhwc || bnh_ok(C, bn_vn(x)), "bn_bwd NHWC: unsupported C=",
+              C);
+  bn_check_like(who, "dy", dy, x, nhwc);
+  bn_check_vec(who, "save_mean", save_mean, C, false);
+  bn_check_vec(who, "save_ivar", save_ivar, C, false);
+  bn_check_vec(who, "weight", weight, C, true);
+  if (conv_present(mask)) {
+    // one bit per element over the flat NHWC index, 8 channels per byte:
+    // only the bf16 (VN = 8) channels_last kernels index it that way
+    TORCH_CHECK(nhwc && x.scalar_type() == torch::kBFloat16,
+                "bn_bwd: mask needs channels_last bf16 x");
+    TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kByte &&
+                    mask.is_contiguous() && mask.numel() == (N * HW * C) >> 3,
+                "bn_bwd: mask must be contiguous uint8 [N*HW*C/8] = [",
+                (N * HW * C) >> 3, "] on GPU");
+  }
+  TORCH_CHECK(!relu || conv_present(mask) || conv_present(y),
+              "bn_bwd: relu needs y/mask");
+  if (relu && conv_present(y)) bn_check_like(who, "y", y, x, nhwc);
   auto f32 = x.options().dtype(torch::kFloat);
   auto dx = torch::empty_like(x);
   auto dres = has_res ? torch::empty_like(x)
@@ -2003,10 +2105,21 @@ std::vector<torch::Tensor> bn_bwd_defer(
     torch::Tensor dz, torch::Tensor x, torch::Tensor z,
     torch::Tensor save_mean, torch::Tensor save_ivar, torch::Tensor weight,
     bool relu, bool has_res) {
-  TORCH_CHECK(x.is_cuda() && dz.is_cuda() &&
-                  x.is_contiguous(at::MemoryFormat::ChannelsLast),
+  const char* who = "bn_bwd_defer";
+  bn_check_x(who, x);
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
               "bn_bwd_defer: channels_last GPU");
   long N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(bnh_ok(C, bn_vn(x)), "bn_bwd_defer: unsupported C=", C);
+  bn_check_like(who, "dz", dz, x, true);
+  // the dres kernel masks by z unconditionally
+  TORCH_CHECK(relu || !has_res, "bn_bwd_defer: has_res needs relu");
+  if (relu) bn_check_like(who, "z", z, x, true);
+  bn_check_vec(who, "save_mean", save_mean, C, false);
+  bn_check_vec(who, "save_ivar", save_ivar, C, false);
+  bn_check_vec(who, "weight", weight, C, true);
+  TORCH_CHECK(!has_res || N * HW * C / bn_vn(x) < (1L << 31),
+              "bn_bwd_defer: N*HW*C too large for the dres pass");
   auto f32 = x.options().dtype(torch::kFloat);
   auto coefs = torch::empty({3, C}, f32);
   auto dweight = torch::empty({C}, f32);
