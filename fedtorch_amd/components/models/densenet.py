@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from fedtorch_amd.ops.batchnorm import BNReLU
+from fedtorch_amd.ops.head import pool_fc
 
 _NUM_CLASSES = {'cifar10': 10, 'cifar100': 100, 'svhn': 10}
 
@@ -101,8 +102,8 @@ class DenseNet(nn.Module):
     def forward(self, x):
         out = self.blocks(self.conv1(x))
         out = self.bn_final(out)
-        out = F.adaptive_avg_pool2d(out, 1).flatten(1)
-        return self.classifier(out)
+        # == classifier(F.adaptive_avg_pool2d(out, 1).flatten(1))
+        return pool_fc(out, self.classifier)
 
 
 def densenet(args):

@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from fedtorch_amd.ops.batchnorm import BNReLU, BNAddReLU
 from fedtorch_amd.ops.conv3x3 import conv_bn_act
+from fedtorch_amd.ops.head import pool_fc
 
 _NUM_CLASSES = {'cifar10': 10, 'cifar100': 100, 'svhn': 10, 'mnist': 10,
                 'fashion_mnist': 10, 'emnist': 10, 'emnist_full': 62,
@@ -137,8 +138,8 @@ class ResNetCifar(_ResNetBase):
     def forward(self, x):
         x = self.bn1(self.conv1(x))
         x = self.layer3(self.layer2(self.layer1(x)))
-        x = self.avgpool(x).flatten(1)
-        return self.fc(x)
+        # == fc(avgpool(x).flatten(1)); one head_fwd launch when opted in
+        return pool_fc(x, self.fc, self.avgpool)
 
 
 class ResNetImageNet(_ResNetBase):
@@ -166,8 +167,8 @@ class ResNetImageNet(_ResNetBase):
     def forward(self, x):
         x = self.maxpool(self.bn1(self.conv1(x)))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-        x = self.avgpool(x).flatten(1)
-        return self.fc(x)
+        # == fc(avgpool(x).flatten(1)); one head_fwd launch when opted in
+        return pool_fc(x, self.fc, self.avgpool)
 
 
 def resnet(args):

@@ -6,6 +6,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from fedtorch_amd.ops.batchnorm import BNReLU
+from fedtorch_amd.ops.head import pool_fc
 
 _NUM_CLASSES = {'cifar10': 10, 'cifar100': 100, 'svhn': 10}
 
@@ -65,8 +66,8 @@ class WideResNet(nn.Module):
     def forward(self, x):
         out = self.blocks(self.conv1(x))
         out = self.bn_final(out)
-        out = F.adaptive_avg_pool2d(out, 1).flatten(1)
-        return self.fc(out)
+        # == fc(F.adaptive_avg_pool2d(out, 1).flatten(1))
+        return pool_fc(out, self.fc)
 
 
 def wideresnet(args):

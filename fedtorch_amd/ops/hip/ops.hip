@@ -18,6 +18,7 @@
 #include "convwrw2.h"
 #include "convfwd.h"
 #include "convs2bwd.h"
+#include "head.h"
 
 #define CHK(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
 #define STREAM at::hip::getCurrentHIPStream().stream()
@@ -2175,7 +2176,180 @@ std::vector<torch::Tensor> bn_bwd_defer(
   return {coefs, dweight, dbias, dres};
 }
 
+// ==========================================================================
+// classifier tail (head.h): pool + FC head fwd/bwd, loss / top-k accumulator
+// ==========================================================================
+static inline bool head_is_float(const torch::Tensor& t) {
+  return t.scalar_type() == torch::kBFloat16 ||
+         t.scalar_type() == torch::kFloat;
+}
+static inline bool head_aligned16(const torch::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// weight [K, C] and bias [K] / empty of the FC layer, any bf16/fp32 mix
+static void head_check_fc(const char* who, const torch::Tensor& weight,
+                          const torch::Tensor& bias, long C,
+                          const torch::Device& dev) {
+  TORCH_CHECK(weight.is_cuda() && weight.device() == dev, who,
+              ": weight must be on x's GPU");
+  TORCH_CHECK(weight.dim() == 2 && weight.is_contiguous(), who,
+              ": weight must be contiguous [K, C]");
+  TORCH_CHECK(head_is_float(weight), who, ": weight must be bf16 or fp32");
+  TORCH_CHECK(weight.size(1) == C, who, ": weight is ", weight.sizes(),
+              ", expected [K, ", C, "]");
+  const long K = weight.size(0);
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= HEAD_MAXC, who,
+              ": unsupported C=", C, " (C % 8 == 0, 8 <= C <= 1024)");
+  TORCH_CHECK(K >= 1 && K <= HEAD_MAXK, who, ": unsupported K=", K,
+              " (1 <= K <= 1024)");
+  TORCH_CHECK(head_aligned16(weight), who, ": weight must be 16-byte aligned");
+  if (bias.numel()) {
+    TORCH_CHECK(bias.is_cuda() && bias.device() == dev, who,
+                ": bias must be on x's GPU");
+    TORCH_CHECK(head_is_float(bias), who, ": bias must be bf16 or fp32");
+    TORCH_CHECK(bias.dim() == 1 && bias.numel() == K && bias.is_contiguous(),
+                who, ": bias must be contiguous [K] = [", K, "] or empty");
+  }
+}
+
+std::vector<torch::Tensor> head_fwd(torch::Tensor x, torch::Tensor weight,
+                                    torch::Tensor bias) {
+  const char* who = "head_fwd";
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4, who, ": x must be 4D on GPU");
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), who,
+              ": channels_last only");
+  TORCH_CHECK(head_is_float(x), who, ": x must be bf16 or fp32");
+  const long N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(N >= 1 && HW >= 1, who, ": empty input");
+  TORCH_CHECK(N < (1L << 31) && HW * C < (1L << 31), who,
+              ": input too large");
+  head_check_fc(who, weight, bias, C, x.device());
+  TORCH_CHECK(head_aligned16(x), who, ": x must be 16-byte aligned");
+  const long K = weight.size(0);
+  auto fopt = x.options().dtype(torch::kFloat).memory_format(
+      at::MemoryFormat::Contiguous);
+  auto logits = torch::empty({N, K}, fopt);
+  auto pooled = torch::empty({N, C}, fopt);
+  const void* bp = bias.numel() ? bias.data_ptr() : nullptr;
+  const int bbf = bias.numel() && bias.scalar_type() == torch::kBFloat16;
+  const bool xb = x.scalar_type() == torch::kBFloat16;
+  const bool wb = weight.scalar_type() == torch::kBFloat16;
+#define HEAD_FWD_LAUNCH(TX, TW)                                              \
+  hipLaunchKernelGGL((head_fwd_k<TX, TW>), dim3((unsigned)N),                \
+                     dim3(FT_BLOCK), 0, STREAM,                              \
+                     reinterpret_cast<const TX*>(x.data_ptr()),              \
+                     reinterpret_cast<const TW*>(weight.data_ptr()), bp,     \
+                     bbf, logits.data_ptr<float>(),                          \
+                     pooled.data_ptr<float>(), (int)C, (int)HW, (int)K)
+  if (xb && wb) HEAD_FWD_LAUNCH(__hip_bfloat16, __hip_bfloat16);
+  else if (xb) HEAD_FWD_LAUNCH(__hip_bfloat16, float);
+  else if (wb) HEAD_FWD_LAUNCH(float, __hip_bfloat16);
+  else HEAD_FWD_LAUNCH(float, float);
+#undef HEAD_FWD_LAUNCH
+  return {logits, pooled};
+}
+
+// returns {dx, dw, db}; dx is undefined (None) without need_dx, db without
+// a bias.  dw / db are fresh contiguous tensors in the parameters' dtypes.
+std::vector<torch::Tensor> head_bwd(torch::Tensor dlogits,
+                                    torch::Tensor pooled,
+                                    torch::Tensor weight, torch::Tensor bias,
+                                    long H, long W, bool x_is_bf16,
+                                    bool need_dx) {
+  const char* who = "head_bwd";
+  TORCH_CHECK(pooled.is_cuda() && pooled.dim() == 2 &&
+                  pooled.scalar_type() == torch::kFloat &&
+                  pooled.is_contiguous(),
+              who, ": pooled must be contiguous fp32 [N, C] on GPU");
+  const long N = pooled.size(0), C = pooled.size(1), HW = H * W;
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, who, ": empty input");
+  TORCH_CHECK(N < (1L << 31) && HW * C < (1L << 31), who,
+              ": input too large");
+  head_check_fc(who, weight, bias, C, pooled.device());
+  const long K = weight.size(0);
+  TORCH_CHECK(dlogits.is_cuda() && dlogits.device() == pooled.device() &&
+                  dlogits.scalar_type() == torch::kFloat &&
+                  dlogits.dim() == 2 && dlogits.size(0) == N &&
+                  dlogits.size(1) == K && dlogits.is_contiguous(),
+              who, ": dlogits must be contiguous fp32 [N, K] = [", N, ", ", K,
+              "] on pooled's GPU");
+  const bool wb = weight.scalar_type() == torch::kBFloat16;
+  torch::Tensor dx, db;
+  auto dw = torch::empty({K, C}, weight.options().memory_format(
+                                     at::MemoryFormat::Contiguous));
+  if (bias.numel())
+    db = torch::empty({K}, bias.options().memory_format(
+                               at::MemoryFormat::Contiguous));
+  if (need_dx) {
+    dx = torch::empty(
+        {N, C, H, W},
+        pooled.options()
+            .dtype(x_is_bf16 ? torch::kBFloat16 : torch::kFloat)
+            .memory_format(at::MemoryFormat::ChannelsLast));
+#define HEAD_DX_LAUNCH(TX, TW)                                               \
+  hipLaunchKernelGGL((head_dx_k<TX, TW>), dim3((unsigned)N), dim3(FT_BLOCK), \
+                     0, STREAM, dlogits.data_ptr<float>(),                   \
+                     reinterpret_cast<const TW*>(weight.data_ptr()),         \
+                     reinterpret_cast<TX*>(dx.data_ptr()), (int)C, (int)HW,  \
+                     (int)K)
+    if (x_is_bf16 && wb) HEAD_DX_LAUNCH(__hip_bfloat16, __hip_bfloat16);
+    else if (x_is_bf16) HEAD_DX_LAUNCH(__hip_bfloat16, float);
+    else if (wb) HEAD_DX_LAUNCH(float, __hip_bfloat16);
+    else HEAD_DX_LAUNCH(float, float);
+#undef HEAD_DX_LAUNCH
+  }
+  hipLaunchKernelGGL(head_dwdb_k, dim3((unsigned)((C + WAVE - 1) / WAVE),
+                                       (unsigned)K),
+                     dim3(FT_BLOCK), 0, STREAM, dlogits.data_ptr<float>(),
+                     pooled.data_ptr<float>(), dw.data_ptr(), wb ? 1 : 0,
+                     db.defined() ? db.data_ptr() : nullptr,
+                     db.defined() && db.scalar_type() == torch::kBFloat16,
+                     (int)N, (int)C, (int)K);
+  return {dx, dw, db};
+}
+
+// acc (fp64 [4] on the GPU) += (loss_sum, top1_count, top5_count, n) of the
+// batch; one launch, one workgroup, no host synchronisation.
+void ce_topk_accum(torch::Tensor logits, torch::Tensor target,
+                   torch::Tensor acc) {
+  const char* who = "ce_topk_accum";
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.is_contiguous(),
+              who, ": logits must be contiguous [N, K] on GPU");
+  TORCH_CHECK(head_is_float(logits), who, ": logits must be bf16 or fp32");
+  const long N = logits.size(0), K = logits.size(1);
+  TORCH_CHECK(K >= 1 && K <= HEAD_MAXK, who, ": unsupported K=", K,
+              " (1 <= K <= 1024)");
+  TORCH_CHECK(N < (1L << 31), who, ": batch too large");
+  TORCH_CHECK(target.is_cuda() && target.device() == logits.device() &&
+                  target.scalar_type() == torch::kLong &&
+                  target.dim() == 1 && target.size(0) == N &&
+                  target.is_contiguous(),
+              who, ": target must be contiguous int64 [N] = [", N,
+              "] on logits' GPU");
+  TORCH_CHECK(acc.is_cuda() && acc.device() == logits.device() &&
+                  acc.scalar_type() == torch::kDouble && acc.dim() == 1 &&
+                  acc.numel() == 4 && acc.is_contiguous(),
+              who, ": acc must be contiguous float64 [4] on logits' GPU");
+  if (N == 0) return;
+  if (logits.scalar_type() == torch::kBFloat16)
+    hipLaunchKernelGGL(ce_topk_k<__hip_bfloat16>, dim3(1),
+                       dim3(HEAD_CE_BLOCK), 0, STREAM,
+                       reinterpret_cast<const __hip_bfloat16*>(
+                           logits.data_ptr()),
+                       target.data_ptr<long>(), acc.data_ptr<double>(),
+                       (int)N, (int)K);
+  else
+    hipLaunchKernelGGL(ce_topk_k<float>, dim3(1), dim3(HEAD_CE_BLOCK), 0,
+                       STREAM, logits.data_ptr<float>(),
+                       target.data_ptr<long>(), acc.data_ptr<double>(),
+                       (int)N, (int)K);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("head_fwd", &head_fwd);
+  m.def("head_bwd", &head_bwd);
+  m.def("ce_topk_accum", &ce_topk_accum);
   m.def("bn_fwd_train", &bn_fwd_train);
   m.def("bn_fwd_train_part", &bn_fwd_train_part);
   m.def("bn_bwd", &bn_bwd);

@@ -34,6 +34,26 @@ def inference_personal(model1, model2, alpha, criterion, metrics, _input,
     return loss, performance
 
 
+def inference_fused(macc, model, criterion, metrics, _input, _target,
+                    model_personal=None, alpha=0.0):
+    """one validation batch on the device-side accumulator
+    (FEDTORCH_FUSED_METRICS, ops/head.py): the logits (blended on the
+    personalised path) go to ONE ce_topk_accum launch and nothing is read
+    back.  Returns None then; a batch the accumulator does not take (logits
+    not 2-D, targets not 1-D int64) gets today's loss + accuracy from the
+    same logits and returns (loss, performance)."""
+    from fedtorch_amd.ops.head import batch_eligible
+    if model_personal is not None:
+        output = alpha * model_personal(_input) + (1 - alpha) * model(_input)
+    else:
+        output = model(_input)
+    if batch_eligible(output, _target):
+        macc.update(output, _target)
+        return None
+    return criterion(output, _target), accuracy(output.data, _target,
+                                                topk=metrics)
+
+
 def do_validate(args, model, optimizer, criterion, metrics, data_loader,
                 group, data_mode='validation', personal=False,
                 model_personal=None, alpha=0.0, local=False, skip=False):
@@ -73,15 +93,28 @@ def do_validate(args, model, optimizer, criterion, metrics, data_loader,
             raise ValueError('model_personal required for personalized '
                              'validation (APFL)')
         model_personal.eval()
+    # device-side loss / top-k accumulation: no per-batch .item(), one
+    # read-back after the loop (ops/head.py; off unless opted in)
+    from fedtorch_amd.ops import head as _head
+    fused, macc = _head.metrics_eligible(args, criterion, metrics), None
     for _input, _target in data_loader:
         _input, _target = _load_data_batch(args, _input, _target)
         if _input.size(0) == 1:
             break  # BatchNorm issue (reference `eval.py:89-91`)
+        if fused and macc is None:
+            macc = _head.MetricAccumulator(_target.device)
         # bf16 twin weights (arena.enable_bf16_compute, hipGraph paths)
         # need autocast in eval too: fp32 inputs vs bf16 conv weights
         from fedtorch_amd.trainings.graphstep import amp as _amp
         with torch.no_grad(), _amp(args):
-            if personal:
+            if macc is not None:
+                out = inference_fused(
+                    macc, model, criterion, metrics, _input, _target,
+                    model_personal if personal else None, alpha)
+                if out is None:
+                    continue
+                loss, performance = out
+            elif personal:
                 loss, performance = inference_personal(
                     model_personal, model, alpha, criterion, metrics,
                     _input, _target)
@@ -91,6 +124,8 @@ def do_validate(args, model, optimizer, criterion, metrics, data_loader,
                     rnn=args.arch == 'rnn')
             tracker = update_performancec_tracker(
                 tracker, loss, performance, _input.size(0))
+    if macc is not None:
+        _head.fill_meters(tracker, macc, metrics)
     model.train()
     if len(metrics) == 1:
         tracker['top5'].count = 1.0

@@ -4,7 +4,9 @@ import numpy as np
 import torch
 
 from fedtorch_amd.components.dataset import _load_data_batch
-from fedtorch_amd.trainings.eval import inference, inference_personal
+from fedtorch_amd.ops import head as _head
+from fedtorch_amd.trainings.eval import (
+    inference, inference_fused, inference_personal)
 from fedtorch_amd.logs.logging import log, update_performancec_tracker
 
 
@@ -27,12 +29,24 @@ def do_validate_centered(args, model, criterion, metrics, optimizer,
         if model_personal is None:
             raise ValueError('model_personal required')
         model_personal.eval()
+    # device-side loss / top-k accumulation: no per-batch .item(), one
+    # read-back after the loop (ops/head.py; off unless opted in)
+    fused, macc = _head.metrics_eligible(args, criterion, metrics), None
     for _input, _target in val_loader:
         _input, _target = _load_data_batch(args, _input, _target)
         if _input.size(0) == 1:
             break
+        if fused and macc is None:
+            macc = _head.MetricAccumulator(_target.device)
         with torch.no_grad():
-            if personal:
+            if macc is not None:
+                out = inference_fused(
+                    macc, model, criterion, metrics, _input, _target,
+                    model_personal if personal else None, alpha)
+                if out is None:
+                    continue
+                loss, performance = out
+            elif personal:
                 loss, performance = inference_personal(
                     model_personal, model, alpha, criterion, metrics,
                     _input, _target)
@@ -42,6 +56,8 @@ def do_validate_centered(args, model, criterion, metrics, optimizer,
                     rnn=args.arch == 'rnn')
             update_performancec_tracker(val_tracker, loss, performance,
                                         _input.size(0))
+    if macc is not None:
+        _head.fill_meters(val_tracker, macc, metrics)
     model.train()
     if personal:
         model_personal.train()
