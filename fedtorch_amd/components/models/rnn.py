@@ -7,6 +7,8 @@ whenever the batch size changes.
 """
 import torch.nn as nn
 
+from fedtorch_amd.ops.gru import gru_seq
+
 
 class CharGRU(nn.Module):
     def __init__(self, dataset, input_size, hidden_size, output_size,
@@ -39,7 +41,7 @@ class CharGRU(nn.Module):
         if self.hidden.device != x.device:
             self.hidden = self.hidden.to(x.device)
         emb = self.encoder(x)
-        out, h = self.gru(emb, self.hidden.detach())
+        out, h = gru_seq(self.gru, emb, self.hidden.detach())
         self.hidden = h.detach()
         out = self.decoder(out)
         # (B, C, T) for CrossEntropyLoss over characters

@@ -19,6 +19,7 @@
 #include "convfwd.h"
 #include "convs2bwd.h"
 #include "head.h"
+#include "gru.h"
 
 #define CHK(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
 #define STREAM at::hip::getCurrentHIPStream().stream()
@@ -2346,7 +2347,118 @@ void ce_topk_accum(torch::Tensor logits, torch::Tensor target,
                        (int)N, (int)K);
 }
 
+// ==========================================================================
+// persistent GRU sequence kernels (gru.h)
+// ==========================================================================
+// fp32 contiguous tensor of the given shape on `dev`
+static void gru_check_f32(const char* who, const char* name,
+                          const torch::Tensor& t, at::IntArrayRef shape,
+                          const torch::Device& dev) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev, who, ": ", name,
+              " must be on gx's GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat, who, ": ", name,
+              " must be fp32");
+  TORCH_CHECK(t.sizes() == shape && t.is_contiguous(), who, ": ", name,
+              " must be contiguous ", shape, ", got ", t.sizes());
+}
+// bf16 / fp32 contiguous parameter of the given shape on `dev`
+static void gru_check_param(const char* who, const char* name,
+                            const torch::Tensor& t, at::IntArrayRef shape,
+                            const torch::Device& dev) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev, who, ": ", name,
+              " must be on gx's GPU");
+  TORCH_CHECK(head_is_float(t), who, ": ", name, " must be bf16 or fp32");
+  TORCH_CHECK(t.sizes() == shape && t.is_contiguous(), who, ": ", name,
+              " must be contiguous ", shape, ", got ", t.sizes());
+}
+static void gru_check_dims(const char* who, long B, long T, long H) {
+  TORCH_CHECK(H >= 1 && H <= GRU_MAXH, who, ": unsupported H=", H,
+              " (1 <= H <= 64)");
+  TORCH_CHECK(B >= 1 && T >= 1, who, ": empty input");
+  TORCH_CHECK(B < (1L << 31) && T < (1L << 31) &&
+                  B * T < (1L << 40), who, ": input too large");
+}
+
+// returns {out [B,T,H], gates [B,T,4,H] = (r,z,n,q)}; gates is an empty
+// tensor without save_gates
+std::vector<torch::Tensor> gru_fwd(torch::Tensor gx, torch::Tensor w_hh,
+                                   torch::Tensor b_hh, torch::Tensor h0,
+                                   bool save_gates) {
+  const char* who = "gru_fwd";
+  TORCH_CHECK(gx.is_cuda() && gx.dim() == 3 && gx.is_contiguous(), who,
+              ": gx must be contiguous [B, T, 3H] on GPU");
+  TORCH_CHECK(gx.scalar_type() == torch::kFloat, who, ": gx must be fp32");
+  TORCH_CHECK(gx.size(2) % 3 == 0, who, ": gx is ", gx.sizes(),
+              ", expected [B, T, 3H]");
+  const long B = gx.size(0), T = gx.size(1), H = gx.size(2) / 3;
+  gru_check_dims(who, B, T, H);
+  const auto dev = gx.device();
+  gru_check_param(who, "w_hh", w_hh, {3 * H, H}, dev);
+  gru_check_param(who, "b_hh", b_hh, {3 * H}, dev);
+  gru_check_f32(who, "h0", h0, {B, H}, dev);
+  auto out = torch::empty({B, T, H}, gx.options());
+  auto gates = save_gates ? torch::empty({B, T, 4, H}, gx.options())
+                          : torch::empty({0}, gx.options());
+  const int wbf = w_hh.scalar_type() == torch::kBFloat16;
+  const int bbf = b_hh.scalar_type() == torch::kBFloat16;
+  const unsigned grid = (unsigned)((B + GRU_ROWS - 1) / GRU_ROWS);
+#define GRU_FWD_LAUNCH(NT)                                                   \
+  hipLaunchKernelGGL(gru_fwd_k<NT>, dim3(grid), dim3(NT * WAVE), 0, STREAM,  \
+                     gx.data_ptr<float>(), w_hh.data_ptr(), wbf,             \
+                     b_hh.data_ptr(), bbf, h0.data_ptr<float>(),             \
+                     out.data_ptr<float>(),                                  \
+                     save_gates ? gates.data_ptr<float>() : nullptr, (int)B, \
+                     (int)T, (int)H)
+  switch ((H + 15) / 16) {
+    case 1: GRU_FWD_LAUNCH(1); break;
+    case 2: GRU_FWD_LAUNCH(2); break;
+    case 3: GRU_FWD_LAUNCH(3); break;
+    default: GRU_FWD_LAUNCH(4); break;
+  }
+#undef GRU_FWD_LAUNCH
+  return {out, gates};
+}
+
+// returns {dgx [B,T,3H], dgh [B,T,3H], dh0 [B,H]}
+std::vector<torch::Tensor> gru_bwd(torch::Tensor dout, torch::Tensor out,
+                                   torch::Tensor gates, torch::Tensor w_hh,
+                                   torch::Tensor h0) {
+  const char* who = "gru_bwd";
+  TORCH_CHECK(out.is_cuda() && out.dim() == 3 && out.is_contiguous(), who,
+              ": out must be contiguous [B, T, H] on GPU");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat, who, ": out must be fp32");
+  const long B = out.size(0), T = out.size(1), H = out.size(2);
+  gru_check_dims(who, B, T, H);
+  const auto dev = out.device();
+  gru_check_f32(who, "dout", dout, {B, T, H}, dev);
+  gru_check_f32(who, "gates", gates, {B, T, 4, H}, dev);
+  gru_check_param(who, "w_hh", w_hh, {3 * H, H}, dev);
+  gru_check_f32(who, "h0", h0, {B, H}, dev);
+  auto dgx = torch::empty({B, T, 3 * H}, out.options());
+  auto dgh = torch::empty({B, T, 3 * H}, out.options());
+  auto dh0 = torch::empty({B, H}, out.options());
+  const int wbf = w_hh.scalar_type() == torch::kBFloat16;
+  const unsigned grid = (unsigned)((B + GRU_ROWS - 1) / GRU_ROWS);
+#define GRU_BWD_LAUNCH(NT)                                                   \
+  hipLaunchKernelGGL(gru_bwd_k<NT>, dim3(grid), dim3(NT * WAVE), 0, STREAM,  \
+                     dout.data_ptr<float>(), out.data_ptr<float>(),          \
+                     gates.data_ptr<float>(), w_hh.data_ptr(), wbf,          \
+                     h0.data_ptr<float>(), dgx.data_ptr<float>(),            \
+                     dgh.data_ptr<float>(), dh0.data_ptr<float>(), (int)B,   \
+                     (int)T, (int)H)
+  switch ((H + 15) / 16) {
+    case 1: GRU_BWD_LAUNCH(1); break;
+    case 2: GRU_BWD_LAUNCH(2); break;
+    case 3: GRU_BWD_LAUNCH(3); break;
+    default: GRU_BWD_LAUNCH(4); break;
+  }
+#undef GRU_BWD_LAUNCH
+  return {dgx, dgh, dh0};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("gru_fwd", &gru_fwd);
+  m.def("gru_bwd", &gru_bwd);
   m.def("head_fwd", &head_fwd);
   m.def("head_bwd", &head_bwd);
   m.def("ce_topk_accum", &ce_topk_accum);
