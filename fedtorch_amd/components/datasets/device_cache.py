@@ -93,20 +93,31 @@ class DeviceCachedLoader(object):
         x2 = torch.take_along_dim(x1, w_idx, dim=3)
         return torch.where(flip.view(B, 1, 1, 1), x2.flip(-1), x2)
 
-    def __iter__(self):
+    def index_batches(self, as_slices=False, device=None):
+        """One epoch's batches as index tensors into ``self.x`` / ``self.y``
+        (int64, on ``device``, default the cache's): the rows ``__iter__``
+        serves, in its order, drawing the epoch's permutation from the
+        generator exactly as it does.  ``as_slices``: an unshuffled loader
+        yields plain slices instead (``__iter__`` serves those as views)."""
         n = len(self.x)
+        device = self._device if device is None else device
         if self.shuffle:
-            perm = torch.randperm(n, generator=self._gen).to(self._device)
+            perm = torch.randperm(n, generator=self._gen).to(device)
         else:
             perm = None
         for b in range(self._nb):
             sl = slice(b * self.batch_size,
                        min((b + 1) * self.batch_size, n))
             if perm is not None:
-                ii = perm[sl]
-                xb, yb = self.x[ii], self.y[ii]
+                yield perm[sl]
+            elif as_slices:
+                yield sl
             else:
-                xb, yb = self.x[sl], self.y[sl]
+                yield torch.arange(sl.start, sl.stop, device=device)
+
+    def __iter__(self):
+        for ii in self.index_batches(as_slices=True):
+            xb, yb = self.x[ii], self.y[ii]
             if self._aug:
                 xb = self._augment(xb)
             yield xb, yb

@@ -286,6 +286,116 @@ def scaffold_control_update(ctrl_new, ctrl_client, ctrl_server, server, client,
 
 
 # --------------------------------------------------------------------------
+# packed linear models: all clients' local steps of a round in ONE launch
+# (hip/linearround.h)
+# --------------------------------------------------------------------------
+
+# LDS floats the kernel declares (159 KiB of a gfx950 CU's 160 KiB); kept
+# equal to LINROUND_LDS_FLOATS of hip/linearround.h (a GPU test compares).
+LINROUND_LDS_FLOATS = 40704
+LINROUND_MAXK = 16
+
+
+def linear_round_lds_floats(F, K, B, uses_momentum):
+    """LDS floats one client needs: the resident [F + 1, K | 1] image of
+    weight and bias (twice with momentum) plus B * (K + 2) of step scratch."""
+    return (2 if uses_momentum else 1) * (F + 1) * (K | 1) + B * (K + 2)
+
+
+def linear_round_max_floats(uses_momentum):
+    """LDS floats left for one client's resident image (F + 1) * (K | 1);
+    the step scratch B * (K + 2) comes off the same budget."""
+    return LINROUND_LDS_FLOATS // (2 if uses_momentum else 1)
+
+
+def linear_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
+                        mom_init, snap, k_cut, *, w_off, b_off, K, loss_kind,
+                        weight_decay, momentum, dampening, nesterov):
+    """All local SGD steps of a round, for every packed client of a linear
+    model, in one call.
+
+    X [M, F] f32, Y [M] (int32 class ids | f32 targets); idx [C, T, B] int32
+    rows of X per sample, -1 = padding; steps [C] int32 (0 = offline, nothing
+    of that client is read or written); lr [C, T] f32; server [N];
+    replicas [C, N] (out); in_mom [C, N] or None/empty; mom_init [C] int32
+    (in/out); snap [C, N] or None/empty: parameters BEFORE step k_cut
+    (1-based), written when 1 <= k_cut <= steps[c].  weight [K, F] sits at
+    `w_off`, bias [K] at `b_off` of the arena; every other element is copied
+    through.  loss_kind 0 = softmax-CE (mean), 1 = MSE (mean, K == 1).
+    The update is the local branch of `fused_sgd_step`.  in_mom / mom_init
+    are touched only when momentum != 0.  Returns loss [C, T]: the mean loss
+    of each executed step, 0 elsewhere."""
+    dev = X.device
+    if in_mom is None:
+        in_mom = torch.empty(0, device=dev)
+    if snap is None:
+        snap = torch.empty(0, device=dev)
+    if _use_hip(X, server, replicas):
+        return _C.linear_local_rounds(
+            X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap,
+            int(k_cut), int(w_off), int(b_off), int(K), int(loss_kind),
+            float(weight_decay), float(momentum), float(dampening),
+            bool(nesterov))
+
+    # eager twin: a per-client, per-step loop; the gradients come from
+    # autograd over F.linear + the loss module's functional, the update from
+    # the fused-SGD twin above over the whole row — the ops of the packed
+    # slot loop, in its order.  Pad gaps (zero in a real arena, where the
+    # whole-row update leaves them zero) are put back afterwards.
+    import torch.nn.functional as Fn
+    C, T, _B = idx.shape
+    Fdim = X.shape[1]
+    nw = K * Fdim
+    use_mom = momentum != 0
+    loss = torch.zeros((C, T), dtype=torch.float32, device=dev)
+    n_steps = steps.tolist()
+    inits = mom_init.tolist()
+    gap = torch.ones_like(server, dtype=torch.bool)
+    gap[w_off:w_off + nw] = False
+    gap[b_off:b_off + K] = False
+    for c in range(C):
+        if n_steps[c] <= 0:
+            continue
+        p = server.clone()
+        grad = torch.zeros_like(p)
+        mom_gaps = in_mom[c][gap].clone() if use_mom else None
+        for s in range(n_steps[c]):
+            if snap.numel() and s + 1 == k_cut:
+                snap[c].copy_(torch.where(gap, server, p))
+            rows = idx[c, s]
+            rows = rows[rows >= 0].long()
+            x = X[rows]
+            w = p[w_off:w_off + nw].view(K, Fdim).clone().requires_grad_(True)
+            b = p[b_off:b_off + K].clone().requires_grad_(True)
+            with torch.enable_grad():
+                out = Fn.linear(x, w, b)
+                if loss_kind == 0:
+                    l = Fn.cross_entropy(out, Y[rows].long())
+                else:
+                    l = Fn.mse_loss(out, Y[rows].unsqueeze(1))
+                gw, gb = torch.autograd.grad(l, (w, b))
+            loss[c, s] = l.detach()
+            grad.zero_()
+            grad[w_off:w_off + nw].copy_(gw.reshape(-1))
+            grad[b_off:b_off + K].copy_(gb)
+            fused_sgd_step(
+                p, grad, lr=float(lr[c, s]), scale=1.0,
+                weight_decay=weight_decay, in_momentum=momentum,
+                out_momentum=0.0, dampening=dampening, nesterov=nesterov,
+                apply_lr=True, apply_in_momentum=use_mom,
+                apply_out_momentum=False,
+                in_buf=in_mom[c] if use_mom else None,
+                first_in=use_mom and not inits[c])
+            if use_mom:
+                inits[c] = 1
+        replicas[c].copy_(torch.where(gap, server, p))
+        if use_mom:
+            in_mom[c][gap] = mom_gaps
+            mom_init[c] = 1
+    return loss
+
+
+# --------------------------------------------------------------------------
 # small host-side math (not perf-critical)
 # --------------------------------------------------------------------------
 

@@ -20,6 +20,7 @@
 #include "convs2bwd.h"
 #include "head.h"
 #include "gru.h"
+#include "linearround.h"
 
 #define CHK(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
 #define STREAM at::hip::getCurrentHIPStream().stream()
@@ -2456,7 +2457,143 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor dout, torch::Tensor out,
   return {dgx, dgh, dh0};
 }
 
+// ==========================================================================
+// packed linear models: all clients' local steps in one launch
+// (linearround.h)
+// ==========================================================================
+// LDS floats one client needs: resident state plus the per-step scratch
+static long linround_lds_need(long F, long K, long B, bool uses_momentum) {
+  return (uses_momentum ? 2 : 1) * (F + 1) * (K | 1) + B * (K + 2);
+}
+// the LDS floats left for one client's resident image, (F + 1) * (K | 1);
+// the B * (K + 2) floats of step scratch come off the same budget
+long linear_round_max_floats(bool uses_momentum) {
+  return LINROUND_LDS_FLOATS / (uses_momentum ? 2 : 1);
+}
+long linear_round_lds_floats(long F, long K, long B, bool uses_momentum) {
+  return linround_lds_need(F, K, B, uses_momentum);
+}
+
+static void linround_check(const char* who, const char* name,
+                           const torch::Tensor& t, at::ScalarType st,
+                           at::IntArrayRef shape, const torch::Device& dev) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev, who, ": ", name,
+              " must be on X's GPU");
+  TORCH_CHECK(t.scalar_type() == st, who, ": ", name, " must be ", st,
+              ", got ", t.scalar_type());
+  TORCH_CHECK(t.sizes() == shape && t.is_contiguous(), who, ": ", name,
+              " must be contiguous ", shape, ", got ", t.sizes());
+}
+
+// returns loss [C, T]; writes replicas / in_mom / mom_init / snap rows of the
+// clients with steps > 0.  idx is range-checked on the host unless the
+// stream is capturing (the kernel itself never reads X outside [0, M)).
+torch::Tensor linear_local_rounds(
+    torch::Tensor X, torch::Tensor Y, torch::Tensor idx, torch::Tensor steps,
+    torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,
+    torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,
+    long k_cut, long w_off, long b_off, long K, long loss_kind,
+    double weight_decay, double momentum, double dampening, bool nesterov) {
+  const char* who = "linear_local_rounds";
+  TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous(), who,
+              ": X must be contiguous [M, F] on GPU");
+  TORCH_CHECK(X.scalar_type() == torch::kFloat, who, ": X must be fp32");
+  const long M = X.size(0), F = X.size(1);
+  const auto dev = X.device();
+  TORCH_CHECK(M >= 1 && F >= 1, who, ": empty X");
+  TORCH_CHECK(M < (1L << 31) && F < (1L << 31), who, ": X too large");
+  TORCH_CHECK(server.dim() == 1 && server.size(0) < (1L << 30), who,
+              ": server must be [N], N < 2^30");
+  TORCH_CHECK(K >= 1 && K <= LINROUND_MAXK, who, ": unsupported K=", K,
+              " (1 <= K <= 16)");
+  TORCH_CHECK(loss_kind == 0 || loss_kind == 1, who, ": loss_kind is ",
+              loss_kind, ", expected 0 (softmax-CE) or 1 (MSE)");
+  TORCH_CHECK(loss_kind == 0 || K == 1, who, ": MSE needs K == 1, got ", K);
+  linround_check(who, "Y", Y, loss_kind == 0 ? torch::kInt : torch::kFloat,
+                 {M}, dev);
+  TORCH_CHECK(idx.dim() == 3, who, ": idx must be [C, T, B], got ",
+              idx.sizes());
+  const long C = idx.size(0), T = idx.size(1), B = idx.size(2);
+  TORCH_CHECK(C >= 1 && T >= 1 && B >= 1, who, ": empty idx");
+  TORCH_CHECK(C < (1L << 31) && T < (1L << 31) && B < (1L << 31), who,
+              ": idx too large");
+  linround_check(who, "idx", idx, torch::kInt, {C, T, B}, dev);
+  linround_check(who, "steps", steps, torch::kInt, {C}, dev);
+  linround_check(who, "lr", lr, torch::kFloat, {C, T}, dev);
+  const long N = server.size(0);
+  linround_check(who, "server", server, torch::kFloat, {N}, dev);
+  linround_check(who, "replicas", replicas, torch::kFloat, {C, N}, dev);
+  linround_check(who, "mom_init", mom_init, torch::kInt, {C}, dev);
+  const bool use_mom = momentum != 0.0;
+  if (use_mom)
+    linround_check(who, "in_mom", in_mom, torch::kFloat, {C, N}, dev);
+  const bool has_snap = snap.numel() != 0;
+  if (has_snap) linround_check(who, "snap", snap, torch::kFloat, {C, N}, dev);
+  TORCH_CHECK(w_off >= 0 && b_off >= 0 && w_off + K * F <= N &&
+                  b_off + K <= N &&
+                  (w_off + K * F <= b_off || b_off + K <= w_off),
+              who, ": weight [", w_off, ", +", K * F, ") / bias [", b_off,
+              ", +", K, ") do not fit the arena of ", N);
+  TORCH_CHECK(!nesterov || (use_mom && dampening == 0.0), who,
+              ": nesterov needs a momentum and zero dampening");
+  const long need = linround_lds_need(F, K, B, use_mom);
+  TORCH_CHECK(need <= LINROUND_LDS_FLOATS, who, ": F=", F, " K=", K, " B=", B,
+              use_mom ? " with" : " without", " momentum needs ", need,
+              " floats of LDS, the limit is ", (long)LINROUND_LDS_FLOATS);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(STREAM, &cap) == hipSuccess, who,
+              ": hipStreamIsCapturing failed");
+  if (cap == hipStreamCaptureStatusNone) {
+    const long top = idx.max().item<int>();
+    TORCH_CHECK(top < M, who, ": idx holds row ", top, " but X has ", M,
+                " rows");
+    const long most = steps.max().item<int>();
+    TORCH_CHECK(most <= T, who, ": steps holds ", most, " but idx has T=", T);
+  }
+
+  auto loss = torch::zeros({C, T}, X.options());
+  LinRoundArgs a;
+  a.X = X.data_ptr<float>();
+  a.Y = Y.data_ptr();
+  a.idx = idx.data_ptr<int>();
+  a.steps = steps.data_ptr<int>();
+  a.lr = lr.data_ptr<float>();
+  a.server = server.data_ptr<float>();
+  a.replicas = replicas.data_ptr<float>();
+  a.in_mom = use_mom ? in_mom.data_ptr<float>() : nullptr;
+  a.mom_init = mom_init.data_ptr<int>();
+  a.snap = has_snap ? snap.data_ptr<float>() : nullptr;
+  a.loss = loss.data_ptr<float>();
+  a.M = (int)M; a.F = (int)F; a.B = (int)B; a.T = (int)T;
+  a.N = (int)N; a.w_off = (int)w_off; a.b_off = (int)b_off;
+  a.k_cut = (int)std::min<long>(std::max<long>(k_cut, 0), 1L << 30);
+  a.use_mom = use_mom; a.nesterov = nesterov;
+  a.wd = (float)weight_decay; a.mom = (float)momentum;
+  a.omd = (float)(1.0 - dampening);
+#define LINROUND_LAUNCH(KK, LOSS)                                            \
+  hipLaunchKernelGGL((linear_round_k<KK, LOSS>), dim3((unsigned)C),          \
+                     dim3(LINROUND_THREADS), 0, STREAM, a)
+#define LINROUND_CASE(KK) case KK: LINROUND_LAUNCH(KK, 0); break
+  if (loss_kind == 1) {
+    LINROUND_LAUNCH(1, 1);
+  } else {
+    switch (K) {
+      LINROUND_CASE(1); LINROUND_CASE(2); LINROUND_CASE(3); LINROUND_CASE(4);
+      LINROUND_CASE(5); LINROUND_CASE(6); LINROUND_CASE(7); LINROUND_CASE(8);
+      LINROUND_CASE(9); LINROUND_CASE(10); LINROUND_CASE(11);
+      LINROUND_CASE(12); LINROUND_CASE(13); LINROUND_CASE(14);
+      LINROUND_CASE(15); LINROUND_CASE(16);
+    }
+  }
+#undef LINROUND_CASE
+#undef LINROUND_LAUNCH
+  return loss;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("linear_local_rounds", &linear_local_rounds);
+  m.def("linear_round_max_floats", &linear_round_max_floats);
+  m.def("linear_round_lds_floats", &linear_round_lds_floats);
   m.def("gru_fwd", &gru_fwd);
   m.def("gru_bwd", &gru_bwd);
   m.def("head_fwd", &head_fwd);

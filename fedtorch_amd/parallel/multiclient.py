@@ -17,11 +17,17 @@ the weighted diffs into ONE per-rank partial, and a single world all-reduce
 finishes the aggregation — identical math to W*C one-client ranks
 (`tests/test_multiclient.py` pins packed(2x2) == flat(4)).
 """
+import os
 from copy import copy
 
 import torch
 
 from fedtorch_amd import ops
+
+# All online clients' local steps of a round in ONE launch for packed linear
+# models (ops.linear_local_rounds, trainings/packed.py).  Opt-in:
+# ``FEDTORCH_PACKED_BATCHED=1``; timings in profiles/packed_linear_notes.md.
+_BATCHED_ENABLED = os.environ.get('FEDTORCH_PACKED_BATCHED', '0') == '1'
 
 
 class VirtualGraph(object):
@@ -67,6 +73,7 @@ class ClientPack(object):
         self.mom_init = [False] * self.C
         self.train_loaders = [None] * self.C
         self.partial = torch.zeros(n, device=dev)
+        self._stacked = None  # (X, Y, row offsets), see stacked_data()
         # per-client BatchNorm running stats (the reference's centered mode
         # gives every ClientCentered its own module and therefore its own
         # BN buffers; the shared compute module must swap them per client)
@@ -113,6 +120,106 @@ class ClientPack(object):
         # counters derived for the last one apply to all (equal splits)
         self.args.num_batches_train_per_device_per_epoch = \
             len(self.train_loaders[0])
+
+    # ---- batched round of a linear model (trainings/packed.py) --------------
+    def linear_layout(self):
+        """(w_off, b_off, K, F) of the compute module's single ``fc`` layer
+        in the arena, or None when the module is not a plain (non-robust)
+        LogisticRegression / LeastSquare."""
+        from fedtorch_amd.components.models.convex import (
+            LogisticRegression, LeastSquare)
+        model, arena = self.base.model, self.base.arena
+        if type(model) not in (LogisticRegression, LeastSquare) \
+                or model.noise is not None:
+            return None
+        if sorted(arena.names) != ['fc.bias', 'fc.weight']:
+            return None
+        w_off = arena.offsets[arena.names.index('fc.weight')]
+        b_off = arena.offsets[arena.names.index('fc.bias')]
+        K, F = model.fc.weight.shape
+        return w_off, b_off, int(K), int(F)
+
+    def batched_blockers(self):
+        """Why this pack's rounds cannot run through
+        ops.linear_local_rounds: a list of reasons, empty when they can."""
+        from fedtorch_amd.components.datasets.device_cache import \
+            DeviceCachedLoader
+        from fedtorch_amd.components.models.convex import LeastSquare
+        args, client = self.args, self.base
+        why = []
+        if not _BATCHED_ENABLED:
+            why.append('FEDTORCH_PACKED_BATCHED is not set')
+        layout = self.linear_layout()
+        if layout is None:
+            why.append('model is not a plain logistic regression / least '
+                       'squares')
+        if getattr(client.arena, 'half_flat', None) is not None \
+                or getattr(args, 'bf16', False):
+            why.append('bf16 compute')
+        if getattr(args, 'federated_type', None) != 'fedavg':
+            why.append('federated_type is not fedavg')
+        opt = client.optimizer
+        if getattr(opt, '_prox_mu', 0.0) != 0.0 or any(
+                getattr(opt, a, None) is not None
+                for a in ('_server', '_ctrl_server', '_ctrl_client',
+                          '_delta')):
+            why.append('a gradient correction is bound on the optimizer')
+        if getattr(args, 'federated_sync_type', None) != 'local_step':
+            why.append('federated_sync_type is not local_step')
+        if getattr(args, 'growing_batch_size', False):
+            why.append('growing_batch_size')
+        loaders = self.train_loaders
+        if not all(isinstance(l, DeviceCachedLoader) and not l._aug
+                   for l in loaders):
+            why.append('a local loader is not an un-augmented '
+                       'DeviceCachedLoader')
+        else:
+            B = loaders[0].batch_size
+            if any(l.batch_size != B for l in loaders):
+                why.append('batch sizes differ between clients')
+            # the slot loop's `break` on a 1-sample batch is not reproduced
+            if any(not l.drop_last and len(l.x) % l.batch_size == 1
+                   for l in loaders):
+                why.append('a partition leaves a 1-sample last batch')
+            if layout is not None:
+                _w, _b, K, F = layout
+                regress = isinstance(client.model, LeastSquare)
+                for l in loaders:
+                    if l.x[0].numel() != F:
+                        why.append('loader rows do not have %d features' % F)
+                        break
+                    if not regress and l.y.is_floating_point():
+                        why.append('class labels are not integers')
+                        break
+                mom = opt.param_groups[0]['in_momentum'] != 0 \
+                    and bool(getattr(args, 'in_momentum', True))
+                need = ops.linear_round_lds_floats(F, K, B, mom)
+                if K > ops.LINROUND_MAXK or need > ops.LINROUND_LDS_FLOATS:
+                    why.append('F=%d K=%d B=%d needs %d LDS floats (limit %d,'
+                               ' K <= %d)' % (F, K, B, need,
+                                              ops.LINROUND_LDS_FLOATS,
+                                              ops.LINROUND_MAXK))
+        return why
+
+    def batched_eligible(self):
+        return not self.batched_blockers()
+
+    def stacked_data(self):
+        """(X [M, F] fp32, Y [M] int32 labels | fp32 targets, offsets [C+1]):
+        the clients' cached partitions stacked; client j's rows are
+        offsets[j] .. offsets[j+1].  Built once, on first use."""
+        if self._stacked is None:
+            from fedtorch_amd.components.models.convex import LeastSquare
+            regress = isinstance(self.base.model, LeastSquare)
+            xs, ys, offs = [], [], [0]
+            for l in self.train_loaders:
+                xs.append(l.x.reshape(len(l.x), -1).float())
+                ys.append(l.y.reshape(-1).float() if regress
+                          else l.y.reshape(-1).to(torch.int32))
+                offs.append(offs[-1] + len(l.x))
+            self._stacked = (torch.cat(xs).contiguous(),
+                             torch.cat(ys).contiguous(), offs)
+        return self._stacked
 
     def run_client(self, j, server_flat, local_step_fn):
         """Swap in client j, run its local steps, swap out.

@@ -81,6 +81,70 @@ def _apply_aggregate(client, server_flat, agg):
         client.work['srv_out_init'] = True
 
 
+def _batched_local_rounds(client, pack, server, online, snap, k_cut):
+    """The local steps of ALL online local clients of a linear model in one
+    ops.linear_local_rounds call (FEDTORCH_PACKED_BATCHED,
+    `ClientPack.batched_eligible`).
+
+    The host first walks the counters exactly as the slot loop does, client
+    by client and step by step, with no GPU work: local_index,
+    local_data_seen, epoch, the scheduled lr and the sync test, pulling each
+    step's rows from the loader's index_batches() (a fresh epoch whenever one
+    runs out, like the `while` / `for` pair of `_local_steps_fn`).  `snap`:
+    DRFA's [C, N] snapshot arena, row j receives client j's parameters before
+    its step `k_cut`."""
+    args = client.args
+    _X, _Y, offs = pack.stacked_data()
+    plan = [None] * pack.C
+    for j in range(pack.C):
+        if pack.global_id(j) not in online:
+            continue
+        plan[j] = []
+        is_sync = False
+        while not is_sync:
+            for rows in pack.train_loaders[j].index_batches(device='cpu'):
+                args.local_index += 1
+                args.local_data_seen += len(rows)
+                get_current_epoch(args)
+                adjust_learning_rate(args, client.optimizer,
+                                     client.scheduler)
+                plan[j].append((rows, client.optimizer.param_groups[0]['lr']))
+                is_sync = is_sync_fed(args)
+                if is_sync:
+                    break
+    T = max([len(p) for p in plan if p] + [1])
+    B = pack.train_loaders[0].batch_size
+    idx = torch.full((pack.C, T, B), -1, dtype=torch.int32)
+    lr = torch.zeros((pack.C, T), dtype=torch.float32)
+    steps = torch.zeros(pack.C, dtype=torch.int32)
+    for j, p in enumerate(plan):
+        if not p:
+            continue
+        steps[j] = len(p)
+        for s, (rows, lr_s) in enumerate(p):
+            idx[j, s, :len(rows)] = rows + offs[j]
+            lr[j, s] = lr_s
+    g = client.optimizer.param_groups[0]
+    momentum = g['in_momentum'] if args.in_momentum else 0.0
+    dev = server.device
+    mom_init = torch.tensor([int(b) for b in pack.mom_init],
+                            dtype=torch.int32).to(dev)
+    w_off, b_off, K, _F = pack.linear_layout()
+    from fedtorch_amd.components.models.convex import LeastSquare
+    loss = ops.linear_local_rounds(
+        _X, _Y, idx.to(dev), steps.to(dev), lr.to(dev), server,
+        pack.replicas, pack.in_mom if momentum != 0 else None, mom_init,
+        snap, k_cut, w_off=w_off, b_off=b_off, K=K,
+        loss_kind=1 if isinstance(client.model, LeastSquare) else 0,
+        weight_decay=g['weight_decay'], momentum=momentum,
+        dampening=g['dampening'], nesterov=g['nesterov'])
+    if pack.in_mom is not None:
+        for j, p in enumerate(plan):
+            if p:
+                pack.mom_init[j] = True
+    return loss
+
+
 def train_and_validate_federated_packed(client, pack, validate=False):
     """FedAvg (optionally DRFA lambda-weighted) over packed virtual
     clients."""
@@ -99,6 +163,14 @@ def train_and_validate_federated_packed(client, pack, validate=False):
         kth_avg = torch.zeros_like(server)
 
     step_fn = _local_steps_fn(client, tracker)
+    # linear models: one launch for all clients' local steps instead of the
+    # slot loop (off unless FEDTORCH_PACKED_BATCHED=1 and the pack qualifies)
+    batched = pack.batched_eligible()
+    log('packed local steps: {}'.format(
+        'one batched launch per round' if batched else 'slot loop'),
+        args.debug)
+    run_client = (lambda j, server_flat, fn: None) if batched \
+        else pack.run_client
     for n_c in range(args.num_comms):
         args.rounds_comm += 1
         args.comm_time.append(0.0)
@@ -156,13 +228,17 @@ def train_and_validate_federated_packed(client, pack, validate=False):
                                 if is_sync:
                                     break
                         return steps
-                    pack.run_client(j, server, step_and_snapshot)
+                    run_client(j, server, step_and_snapshot)
                 else:
                     w = 1.0 / n_online
-                    pack.run_client(j, server, step_fn)
+                    run_client(j, server, step_fn)
             else:
                 w = 0.0
             weights.append(w)
+        if batched:
+            _batched_local_rounds(client, pack, server, online,
+                                  kth if drfa else None,
+                                  k_cut if drfa else 0)
 
         partial = pack.accumulate_partial(server, weights)
         client.comm.all_reduce(partial)

@@ -1,0 +1,128 @@
+# -*- coding: utf-8 -*-
+"""Packed linear models: time per federated round of the slot loop
+(FEDTORCH_PACKED_BATCHED off: per client and step one eager forward,
+backward and fused SGD launch) against the batched round (on: ONE
+linear_local_rounds launch for all clients, hip/linearround.h).  Needs a GPU.
+
+Configurations: synthetic logistic regression (60 -> 10) and MNIST logistic
+regression (784 -> 10), B = 50, tau = 10, C in {16, 128} virtual clients on
+one rank, every client online, momentum 0.9 on and off.
+
+Per configuration ONE process builds the federation once, warms both paths
+up, then runs --rounds rounds of each path ALTERNATELY; a round is timed
+wall-clock between two device synchronisations (it includes the host's plan
+walk, the aggregation and the replica re-sync, which both paths share).  The
+range of each path is printed so the spread is visible.  The loaders, the
+counters and the model carry on from round to round; both paths consume
+them alike."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from fedtorch_amd import ops  # noqa: E402
+from fedtorch_amd.parallel import multiclient  # noqa: E402
+
+B, TAU = 50, 10
+
+
+def federation(data, C, momentum):
+    from fedtorch_amd.parameters import get_args
+    from fedtorch_amd.nodes import Client
+    os.environ['FEDTORCH_SYNTH_SIZE'] = str(C * 500)
+    torch.manual_seed(1)
+    np.random.seed(1)
+    argv = ['-d', data, '-a', 'logistic_regression', '-f', 'true',
+            '--federated_type', 'fedavg', '--num_comms', '1',
+            '--clients_per_rank', str(C), '-b', str(B), '--lr', '0.05',
+            '--federated_sync_type', 'local_step', '--local_step', str(TAU),
+            '--online_client_rate', '1.0',
+            '--in_momentum', 'true' if momentum else 'false',
+            '--in_momentum_factor', '0.9', '--weight_decay', '1e-4',
+            '--stop_criteria', 'epoch', '--num_epochs', '1000',
+            '--on_cuda', 'true', '-j', '0', '--manual_seed', '7',
+            '--checkpoint', '/tmp/ft_packed_linear_micro', '--debug',
+            'false']
+    if data == 'synthetic':
+        argv += ['--iid_data', 'false']
+    client = Client(get_args(argv), 0)
+    client.initialize()
+    client.initialize_dataset()
+    client.load_local_dataset()
+    client.gen_aux_models()
+    pack = multiclient.ClientPack(client, C)
+    pack.build_loaders()
+    # the slot loop ends a client's epoch on a 1-sample batch, which the
+    # batched round does not reproduce: drop that sample for BOTH paths
+    cut = 0
+    for ld in pack.train_loaders:
+        if len(ld.x) % ld.batch_size == 1:
+            ld.x, ld.y = ld.x[:-1], ld.y[:-1]
+            ld._nb = (len(ld.x) + ld.batch_size - 1) // ld.batch_size
+            cut += 1
+    if cut:
+        print('  (%d client partitions shortened by one sample)' % cut)
+    return client, pack
+
+
+def one_round(client, pack, batched):
+    from fedtorch_amd.trainings.packed import \
+        train_and_validate_federated_packed
+    multiclient._BATCHED_ENABLED = batched
+    assert pack.batched_eligible() == batched, pack.batched_blockers()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    train_and_validate_federated_packed(client, pack)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--clients', type=str, default='16,128')
+    ap.add_argument('--data', type=str, default='synthetic,mnist')
+    a = ap.parse_args()
+    if not (torch.cuda.is_available() and ops.hip_available()):
+        raise SystemExit('packed_linear_micro needs a GPU and the built '
+                         'kernel pack')
+    old = multiclient._BATCHED_ENABLED
+    try:
+        for data in a.data.split(','):
+            for C in [int(c) for c in a.clients.split(',')]:
+                for momentum in (True, False):
+                    tag = '%s C=%d momentum=%s' % (data, C,
+                                                   'on' if momentum else 'off')
+                    client, pack = federation(data, C, momentum)
+                    for _ in range(a.warmup):
+                        for batched in (False, True):
+                            one_round(client, pack, batched)
+                    t = {False: [], True: []}
+                    for _ in range(a.rounds):
+                        for batched in (False, True):
+                            t[batched].append(one_round(client, pack,
+                                                        batched))
+                    s, f = t[False], t[True]
+                    print('%s ms/round: slot loop [%.2f, %.2f] median %.2f | '
+                          'batched [%.2f, %.2f] median %.2f | %s; median '
+                          'ratio %.1f' % (
+                              tag, min(s), max(s), statistics.median(s),
+                              min(f), max(f), statistics.median(f),
+                              'disjoint, below' if max(f) < min(s) else
+                              'disjoint, above' if min(f) > max(s)
+                              else 'overlap',
+                              statistics.median(s) / statistics.median(f)),
+                          flush=True)
+    finally:
+        multiclient._BATCHED_ENABLED = old
+    print('PACKED_LINEAR_MICRO_OK')
+
+
+if __name__ == '__main__':
+    main()
