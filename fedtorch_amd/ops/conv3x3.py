@@ -1,5 +1,9 @@
 # -*- coding: utf-8 -*-
-"""NHWC 3x3 convolution modules on the MFMA kernel pack (round 2).
+"""NHWC 3x3 convolution modules on the MFMA kernel pack.
+
+Routing lives in three small functions: `_mfma_stride` (is this a shape
+the kernels cover), `_kernels_active` (GPU, extension, eager not forced)
+and `_bwd_plan` (which dx / dw path a body conv's backward takes).
 
 Default GPU training path for the CIFAR ResNet body convs (Co == Ci,
 (Co, W) in {(16,32), (32,16), (64,8)}) and the stride-2 transitions:
@@ -41,7 +45,11 @@ import torch.nn.functional as F
 from fedtorch_amd import ops
 
 _CL = torch.channels_last
-_SHAPES = {(16, 32), (32, 16), (64, 8)}
+# what the kernels are built for (the instance table of hip/ops.hip): the
+# body convs as (C, W) with Co == Ci at stride 1, the transitions as
+# (Ci, W_in) with Co == 2 Ci at stride 2
+_SHAPES = {(64, 8), (32, 16), (16, 32)}
+_S2_SHAPES = {(16, 32), (32, 16)}
 # Default OFF: the kernel is numerically exact (test_conv3x3_wrw_*) but at
 # CIFAR sizes it measured 27-79 us/call vs MIOpen's 22-33 us (the LDS-staged
 # tile pipeline is latency-bound at these tiny K-tiles; see
@@ -101,6 +109,20 @@ def bn_defer_active():
 
 def register_bn_defer(grad, xbn, z, coefs, relu, dres=None):
     _BNBWD_TAGS[grad.data_ptr()] = (xbn, z, coefs, relu, dres)
+
+
+def _pop_bn_tag(dy):
+    """(channels_last dy, its deferred-BN tag or None).  The tag is popped
+    by the INCOMING tensor's ptr before the contiguous() copy could change
+    it, then again by the copy's (a missed tag would silently skip the BN
+    backward transform)."""
+    tag = _BNBWD_TAGS.pop(dy.data_ptr(), None) if _BNBWD_TAGS else None
+    dy = dy.contiguous(memory_format=_CL)
+    if tag is None and _BNBWD_TAGS:
+        tag = _BNBWD_TAGS.pop(dy.data_ptr(), None)
+    return dy, tag
+
+
 _EMPTY = {}
 
 
@@ -111,11 +133,67 @@ def _empty(dev):
     return e
 
 
+def _kernels_active(x):
+    """the one runtime gate of every kernel route: a GPU tensor, the
+    extension built, eager not forced"""
+    return x.is_cuda and ops.hip_available() and not ops.FORCE_EAGER
+
+
+def _mfma_stride(conv, x, v1_rows=False):
+    """1 / 2 when `conv` on `x` is a shape the MFMA conv kernels cover, else
+    0.  Shape, dtype and layout only, so it holds on CPU tensors too; the
+    flags and `_kernels_active` are the caller's.  The stride-1 kernels
+    tile H by 8 rows; wrw v1 (`v1_rows`) by its 32-position K-tile."""
+    if not (x.dim() == 4 and conv.bias is None and conv.padding == (1, 1)
+            and x.dtype == torch.bfloat16
+            and x.is_contiguous(memory_format=_CL)):
+        return 0
+    Ci, Co, H, W = conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]
+    if conv.stride == (1, 1) and Co == Ci and (Ci, W) in _SHAPES:
+        return int(H % (32 // W if v1_rows else 8) == 0)
+    if (conv.stride == (2, 2) and Co == 2 * Ci and (Ci, W) in _S2_SHAPES
+            and H % 16 == 0):
+        return 2
+    return 0
+
+
+def _kernel_weight(w):
+    """w as the kernels read it, bf16 channels_last, or None"""
+    wb = w if w.dtype == torch.bfloat16 else \
+        w.bfloat16().contiguous(memory_format=_CL)
+    return wb if wb.is_contiguous(memory_format=_CL) else None
+
+
+def _lib_backward(dy, x, weight, stride, want_dx, want_dw):
+    """(dx, dw) of a 3x3/p1 conv from ONE aten.convolution_backward call,
+    None for the one not wanted"""
+    dx, dw, _ = torch.ops.aten.convolution_backward(
+        dy, x, weight, None, [stride, stride], [1, 1], [1, 1], False, [0, 0],
+        1, [want_dx, want_dw, False])
+    return dx, dw
+
+
+def _bwd_plan(C, tagged):
+    """(dx path, dw path, combined) of a body conv's backward, from the
+    module flags and the channel count.  dx: 'dgrad' | 'lib', with a live
+    deferred-BN tag always 'dgrad_bn' (the BN already SKIPPED its dx pass;
+    ignoring the tag would treat dz as dy_conv silently).  dw: 'wrw2' |
+    'wrw' (v1, never on a tag's dy_conv) | 'lib'.  combined: both on the
+    library, which is ONE call (dgrad+wrw split into two was ~0.2 ms/step
+    slower over the 19 body convs)."""
+    wrw2 = _WRW2_ENABLED or C in _WRW2_SHAPES
+    if tagged:
+        return 'dgrad_bn', 'wrw2' if wrw2 else 'lib', False
+    dx = 'dgrad' if _DGRAD_ENABLED else 'lib'
+    dw = 'wrw2' if wrw2 else 'wrw' if _ENABLED else 'lib'
+    return dx, dw, dx == dw == 'lib'
+
+
 class _Conv3x3BNFn(torch.autograd.Function):
     """y, part = conv3x3(x, w) with the BN-stats partials [grid, Co, 2]
     produced by the conv epilogue (consumed by bn_fwd_train_part so the
-    following BN skips its stats pass).  Backward: dgrad/wrw via the same
-    paths as _Conv3x3Fn."""
+    following BN skips its stats pass).  Backward: dx and dw each by the
+    path `_bwd_plan` names."""
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -134,58 +212,31 @@ class _Conv3x3BNFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dpart):
         x, weight = ctx.saved_tensors
-        # pop the deferred-BN tag by the INCOMING tensor's ptr before any
-        # contiguous() copy could change it (a missed tag would silently
-        # skip the BN backward transform)
-        tag = _BNBWD_TAGS.pop(dy.data_ptr(), None) if _BNBWD_TAGS else None
-        dy = dy.contiguous(memory_format=_CL)
-        if tag is None and _BNBWD_TAGS:
-            tag = _BNBWD_TAGS.pop(dy.data_ptr(), None)
-        # a live tag means the BN already SKIPPED its dx pass: always
-        # honor it (ignoring it would treat dz as dy_conv silently)
-        if tag is not None:
+        dy, tag = _pop_bn_tag(dy)
+        need_dx = bool(ctx.needs_input_grad[0])
+        dx_path, dw_path, combined = _bwd_plan(weight.shape[0],
+                                               tag is not None)
+        if combined:
+            return _lib_backward(dy, x, weight, 1, need_dx, True)
+        dx = None
+        if dx_path == 'dgrad_bn':
+            # dy is dz here; the kernel also hands back dy_conv for the wrw
             xbn, z, coefs, relu, dres = tag
-            e = _empty(dy.device)
-            dx, dyc = ops._C.conv3x3_dgrad_bn(
+            dx, dy = ops._C.conv3x3_dgrad_bn(
                 dy, weight, xbn, z if z is not None else xbn, coefs, relu,
-                dres if dres is not None else e)
-            if not ctx.needs_input_grad[0]:
+                dres if dres is not None else _empty(dy.device))
+            if not need_dx:
                 dx = None
-            if _WRW2_ENABLED or weight.shape[0] in _WRW2_SHAPES:
-                dw = ops._C.conv3x3_wrw2(dyc, x)
-            else:
-                dw = torch.ops.aten.convolution_backward(
-                    dyc, x, weight, None, [1, 1], [1, 1], [1, 1], False,
-                    [0, 0], 1, [False, True, False])[1]
-            return dx, dw
-        use_wrw2 = _WRW2_ENABLED or weight.shape[0] in _WRW2_SHAPES
-        custom_dx = _DGRAD_ENABLED
-        custom_dw = use_wrw2 or _ENABLED
-        if custom_dx and custom_dw:
-            dx = ops._C.conv3x3_dgrad(dy, weight) \
-                if ctx.needs_input_grad[0] else None
-            dw = ops._C.conv3x3_wrw2(dy, x) if use_wrw2 \
-                else ops._C.conv3x3_wrw(dy, x)
-        elif custom_dx:
-            dx = ops._C.conv3x3_dgrad(dy, weight) \
-                if ctx.needs_input_grad[0] else None
-            dw = torch.ops.aten.convolution_backward(
-                dy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0],
-                1, [False, True, False])[1]
-        elif custom_dw:
-            dx = None
-            if ctx.needs_input_grad[0]:
-                dx = torch.ops.aten.convolution_backward(
-                    dy, x, weight, None, [1, 1], [1, 1], [1, 1], False,
-                    [0, 0], 1, [True, False, False])[0]
-            dw = ops._C.conv3x3_wrw2(dy, x) if use_wrw2 \
-                else ops._C.conv3x3_wrw(dy, x)
+        elif need_dx and dx_path == 'dgrad':
+            dx = ops._C.conv3x3_dgrad(dy, weight)
+        elif need_dx:
+            dx = _lib_backward(dy, x, weight, 1, True, False)[0]
+        if dw_path == 'wrw2':
+            dw = ops._C.conv3x3_wrw2(dy, x)
+        elif dw_path == 'wrw':
+            dw = ops._C.conv3x3_wrw(dy, x)
         else:
-            # ONE combined call (dgrad+wrw split into two was ~0.2 ms/step
-            # slower over the 19 body convs)
-            dx, dw, _ = torch.ops.aten.convolution_backward(
-                dy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0],
-                1, [bool(ctx.needs_input_grad[0]), True, False])
+            dw = _lib_backward(dy, x, weight, 1, False, True)[1]
         return dx, dw
 
 
@@ -210,10 +261,8 @@ class _Conv3x3S2BNFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dpart):
         x, weight = ctx.saved_tensors
-        tag = _BNBWD_TAGS.pop(dy.data_ptr(), None) if _BNBWD_TAGS else None
-        dy = dy.contiguous(memory_format=_CL)
-        if tag is None and _BNBWD_TAGS:
-            tag = _BNBWD_TAGS.pop(dy.data_ptr(), None)
+        dy, tag = _pop_bn_tag(dy)
+        need_dx = bool(ctx.needs_input_grad[0])
         if tag is not None:
             # a deferred BN backward landed on the stride-2 conv (no TRF
             # kernel here): materialize dy_conv = A*mask(dz) + B + D*x_bn
@@ -230,18 +279,17 @@ class _Conv3x3S2BNFn(torch.autograd.Function):
             D = coefs[2].view(1, C, 1, 1)
             dy = (g.float() * A + B + D * xbn.float()).bfloat16() \
                 .contiguous(memory_format=_CL)
-        if _S2BWD_ENABLED and ops.hip_available() and not ops.FORCE_EAGER:
-            dx = ops._C.conv3x3s2_dgrad(dy, weight) \
-                if ctx.needs_input_grad[0] else None
+        if _S2BWD_ENABLED and _kernels_active(dy):
+            dx = ops._C.conv3x3s2_dgrad(dy, weight) if need_dx else None
             dw = ops._C.conv3x3s2_wrw(dy, x)
             return dx, dw
-        dx, dw, _ = torch.ops.aten.convolution_backward(
-            dy, x, weight, None, [2, 2], [1, 1], [1, 1], False, [0, 0],
-            1, [bool(ctx.needs_input_grad[0]), True, False])
-        return dx, dw
+        return _lib_backward(dy, x, weight, 2, need_dx, True)
 
 
 class _Conv3x3Fn(torch.autograd.Function):
+    """stock forward; backward with the wrw v1 weight gradient (opt-in
+    FEDTORCH_MFMA_WRW, taken only when the fused forward did not apply)"""
+
     @staticmethod
     def forward(ctx, x, weight):
         y = F.conv2d(x, weight, None, (1, 1), (1, 1))
@@ -252,11 +300,8 @@ class _Conv3x3Fn(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         dy = dy.contiguous(memory_format=_CL)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.ops.aten.convolution_backward(
-                dy, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0],
-                1, [True, False, False])[0]
+        dx = _lib_backward(dy, x, weight, 1, True, False)[0] \
+            if ctx.needs_input_grad[0] else None
         dw = ops._C.conv3x3_wrw(dy, x)
         return dx, dw
 
@@ -328,65 +373,38 @@ class NhwcConv1x1S2(nn.Conv2d):
 
 
 class NhwcConv3x3(nn.Conv2d):
-    """Drop-in 3x3/s1/p1 bias-free Conv2d whose channels_last bf16 GPU path
-    uses the MFMA wrw kernel.  state_dict layout is the stock Conv2d's."""
+    """Drop-in 3x3/p1 bias-free Conv2d (stride 1 or 2) with the stock
+    Conv2d's state_dict layout.  In training, on a bf16 channels_last GPU
+    input of a shape `_mfma_stride` accepts, the forward is the MFMA kernel
+    with the BN-stats epilogue and the backward is `_Conv3x3BNFn` /
+    `_Conv3x3S2BNFn`'s; the eval-mode launch is `conv_bn_act`'s.  Anything
+    else is exactly F.conv2d."""
 
     def forward(self, x):
         w = self.weight
-        use_fwd = (_FWD_ENABLED and self.training and x.is_cuda
-                   and x.dim() == 4 and self.bias is None
-                   and self.stride == (1, 1) and self.padding == (1, 1)
-                   and x.dtype == torch.bfloat16
-                   and self.in_channels == self.out_channels
-                   and (self.out_channels, x.shape[3]) in _SHAPES
-                   and x.shape[2] % 8 == 0
-                   and x.is_contiguous(memory_format=_CL)
-                   and ops.hip_available() and not ops.FORCE_EAGER)
-        if use_fwd:
-            wb = w if w.dtype == torch.bfloat16 else \
-                w.bfloat16().contiguous(memory_format=_CL)
-            if wb.is_contiguous(memory_format=_CL):
-                y, part = _Conv3x3BNFn.apply(x, wb)
+        if self.training and _kernels_active(x):
+            stride = _mfma_stride(self, x) if _FWD_ENABLED else 0
+            wb = _kernel_weight(w) if stride else None
+            if wb is not None:
+                fn = _Conv3x3BNFn if stride == 1 else _Conv3x3S2BNFn
+                y, part = fn.apply(x, wb)
                 y._ft_bn_part = part  # consumed by FusedBatchNorm2d
                 return y
-        use_s2 = (_FWD_ENABLED and self.training and x.is_cuda
-                  and x.dim() == 4 and self.bias is None
-                  and self.stride == (2, 2) and self.padding == (1, 1)
-                  and x.dtype == torch.bfloat16
-                  and self.out_channels == 2 * self.in_channels
-                  and (self.in_channels, x.shape[3]) in ((16, 32), (32, 16))
-                  and x.shape[2] % 16 == 0
-                  and x.is_contiguous(memory_format=_CL)
-                  and ops.hip_available() and not ops.FORCE_EAGER)
-        if use_s2:
-            wb = w if w.dtype == torch.bfloat16 else \
-                w.bfloat16().contiguous(memory_format=_CL)
-            if wb.is_contiguous(memory_format=_CL):
-                y, part = _Conv3x3S2BNFn.apply(x, wb)
-                y._ft_bn_part = part
-                return y
-        use = (_ENABLED and torch.is_grad_enabled() and self.training
-               and x.is_cuda
-               and x.dim() == 4 and self.bias is None
-               and self.stride == (1, 1) and self.padding == (1, 1)
-               and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
-               and self.in_channels == self.out_channels
-               and (self.out_channels, x.shape[3]) in _SHAPES
-               and x.shape[2] % (32 // x.shape[3]) == 0
-               and x.is_contiguous(memory_format=_CL)
-               and w.is_contiguous(memory_format=_CL)
-               and ops.hip_available() and not ops.FORCE_EAGER)
-        if not use:
-            return F.conv2d(x, w, self.bias, self.stride, self.padding,
-                            self.dilation, self.groups)
-        return _Conv3x3Fn.apply(x, w)
+            # wrw v1 (opt-in) under the stock forward, on its own conditions
+            if (_ENABLED and torch.is_grad_enabled()
+                    and w.dtype == torch.bfloat16
+                    and w.is_contiguous(memory_format=_CL)
+                    and _mfma_stride(self, x, v1_rows=True) == 1):
+                return _Conv3x3Fn.apply(x, w)
+        return F.conv2d(x, w, self.bias, self.stride, self.padding,
+                        self.dilation, self.groups)
 
 
 def eval_active(x):
     """the eval-mode kernel path applies to this call (the module's own
     `not self.training` is checked by the caller, first)"""
-    return (_EVAL_ENABLED and not torch.is_grad_enabled() and x.is_cuda
-            and ops.hip_available() and not ops.FORCE_EAGER)
+    return (_EVAL_ENABLED and not torch.is_grad_enabled()
+            and _kernels_active(x))
 
 
 def bn_eval_ok(bn):
@@ -396,25 +414,6 @@ def bn_eval_ok(bn):
             and bn.weight is not None and bn.bias is not None
             and bn.weight.dtype == torch.float32
             and bn.running_mean.dtype == torch.float32)
-
-
-def _eval_conv_stride(conv, x):
-    """1 / 2 when `conv` on `x` is a shape the MFMA forward kernels cover
-    (the training path's shape, dtype and layout conditions), else 0"""
-    if not (x.dim() == 4 and conv.bias is None and conv.padding == (1, 1)
-            and x.dtype == torch.bfloat16
-            and x.is_contiguous(memory_format=_CL)):
-        return 0
-    if (conv.stride == (1, 1) and conv.in_channels == conv.out_channels
-            and (conv.out_channels, x.shape[3]) in _SHAPES
-            and x.shape[2] % 8 == 0):
-        return 1
-    if (conv.stride == (2, 2)
-            and conv.out_channels == 2 * conv.in_channels
-            and (conv.in_channels, x.shape[3]) in ((16, 32), (32, 16))
-            and x.shape[2] % 16 == 0):
-        return 2
-    return 0
 
 
 def conv_bn_act(conv, bn_mod, x, res=None):
@@ -434,16 +433,13 @@ def conv_bn_act(conv, bn_mod, x, res=None):
                 and (has_res or isinstance(bn_mod, BNReLU))
                 and has_res == (res is not None) and bn_eval_ok(bn)
                 and (res is None or res.dtype == torch.bfloat16)):
-            stride = _eval_conv_stride(conv, x)
-        if stride:
-            w = conv.weight
-            wb = w if w.dtype == torch.bfloat16 else \
-                w.bfloat16().contiguous(memory_format=_CL)
-            if wb.is_contiguous(memory_format=_CL):
-                rc = res.contiguous(memory_format=_CL) if has_res \
-                    else _empty(x.device)
-                return ops._C.conv3x3_bn_act_fwd(
-                    x, wb, bn.weight, bn.bias, bn.running_mean,
-                    bn.running_var, float(bn.eps), True, rc, stride)
+            stride = _mfma_stride(conv, x)
+        wb = _kernel_weight(conv.weight) if stride else None
+        if wb is not None:
+            rc = res.contiguous(memory_format=_CL) if has_res \
+                else _empty(x.device)
+            return ops._C.conv3x3_bn_act_fwd(
+                x, wb, bn.weight, bn.bias, bn.running_mean,
+                bn.running_var, float(bn.eps), True, rc, stride)
     y = conv(x)
     return bn_mod(y) if res is None else bn_mod(y, res)

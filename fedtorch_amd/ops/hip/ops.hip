@@ -868,6 +868,120 @@ void cast_to_half(torch::Tensor src, torch::Tensor dst) {
 }
 
 // ==========================================================================
+// What the 3x3 conv launchers share: the instance table, the dispatch over
+// it, the argument checks and the pointer casts
+// ==========================================================================
+// One (channels, width, stride) instance the conv kernels are built for.
+// W is the OUTPUT width, as the kernels expect; a launcher sees W_IN.
+template <int CI_, int CO_, int CO_TILE_, int W_, int S_>
+struct ConvInst {
+  static constexpr int CI = CI_, CO = CO_, CO_TILE = CO_TILE_, W = W_, S = S_;
+  static constexpr int W_IN = W * S;
+  static constexpr int SPLIT = CO / CO_TILE;  // workgroups per 8-row tile
+};
+
+template <class... I>
+struct ConvInstList {};
+
+// the ResNet body convs (Co == Ci, stride 1) and the two transitions
+// (Co == 2 Ci, stride 2): THE shape table of every launcher below
+using ConvInsts = ConvInstList<
+    ConvInst<16, 16, 16, 32, 1>, ConvInst<32, 32, 32, 16, 1>,
+    ConvInst<64, 64, 32, 8, 1>, ConvInst<16, 32, 32, 16, 2>,
+    ConvInst<32, 64, 32, 8, 2>>;
+
+template <int S, class F, class... I>
+static inline bool conv_match(ConvInstList<I...>, int Ci, int Co, int W_in,
+                              F& f) {
+  auto one = [&](auto inst) {
+    using T = decltype(inst);
+    if constexpr (T::S == S) {
+      if (Ci == T::CI && Co == T::CO && W_in == T::W_IN) {
+        f(inst);
+        return true;
+      }
+    }
+    return false;
+  };
+  return (one(I{}) || ...);
+}
+
+// f(ConvInst<...>{}) for the stride-S instance that matches, else the
+// "unsupported" error.  S is a template argument so that a launcher
+// instantiates its kernels for the instances of its own stride only.
+template <int S, class F>
+static inline void conv_dispatch(const char* who, int Ci, int Co, int W_in,
+                                 F&& f) {
+  TORCH_CHECK(conv_match<S>(ConvInsts{}, Ci, Co, W_in, f), who,
+              ": unsupported (Ci,Co,W)=", Ci, ",", Co, ",", W_in,
+              " at stride ", S);
+}
+
+// a runtime flag as the std::bool_constant a kernel's template flag takes
+template <class F>
+static inline void bool_dispatch(bool b, F&& f) {
+  if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+static inline const __hip_bfloat16* bf16_ptr(const torch::Tensor& t) {
+  return reinterpret_cast<const __hip_bfloat16*>(t.data_ptr());
+}
+
+static inline __hip_bfloat16* bf16_out(const torch::Tensor& t) {
+  return reinterpret_cast<__hip_bfloat16*>(t.data_ptr());
+}
+
+// argument checks: the kernels index every pointer from the activation's
+// sizes alone, so each tensor handed to them is validated here.  Optional
+// arguments are absent when empty.
+static inline bool conv_present(const torch::Tensor& t) {
+  return t.defined() && t.numel() > 0;
+}
+
+// t: 4D bf16 channels_last on the GPU (activations, gradients, weights)
+static inline void conv_check_act(const char* who, const char* name,
+                                  const torch::Tensor& t) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4, who, ": ", name,
+              " must be 4D on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, who, ": ", name,
+              " must be bf16");
+  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), who, ": ",
+              name, " must be channels_last");
+}
+
+// t: conv_check_act with exactly these sizes
+static inline void conv_check_like(const char* who, const char* name,
+                                   const torch::Tensor& t,
+                                   at::IntArrayRef sizes) {
+  conv_check_act(who, name, t);
+  TORCH_CHECK(t.sizes() == sizes, who, ": ", name, " must be ", sizes);
+}
+
+// dy of a weight-gradient launcher: the gradient of an [N, Co, H, W] output
+static inline void conv_check_dy(const char* who, const torch::Tensor& dy,
+                                 int N, int H, int W) {
+  conv_check_act(who, "dy", dy);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W, who,
+              ": dy must be [N, Co, H, W] = [", N, ", Co, ", H, ", ", W, "]");
+}
+
+// w, after conv_check_act: [Co, Ci, 3, 3] (memory [Co][3][3][Ci])
+static inline void conv_check_w(const char* who, const torch::Tensor& w,
+                                int Co, int Ci) {
+  TORCH_CHECK(w.size(0) == Co && w.size(1) == Ci && w.size(2) == 3 &&
+                  w.size(3) == 3,
+              who, ": w must be [Co, Ci, 3, 3] = [", Co, ", ", Ci,
+              ", 3, 3]");
+}
+
+// a new channels_last tensor of t's dtype and device
+static inline torch::Tensor conv_empty(const torch::Tensor& t,
+                                       at::IntArrayRef sizes) {
+  return torch::empty(
+      sizes, t.options().memory_format(at::MemoryFormat::ChannelsLast));
+}
+
+// ==========================================================================
 // MFMA wrw v2 (convwrw2.h): transposed LDS staging, alignbit tap shifts
 // ==========================================================================
 // supertile streams launched at most (a stream = the G workgroups that share
@@ -882,58 +996,47 @@ int conv3x3_wrw2_grid_cap(int C) {
   return cap > 0 ? cap : (C == 16 ? 256 : C == 32 ? 128 : 64);
 }
 
-template <int CO, int W, int COW, int CIWV, int NB, int CW>
-static void conv3x3_wrw2_launch(const torch::Tensor& dy,
-                                const torch::Tensor& x, torch::Tensor& dw,
-                                int N, int H) {
-  using C = Wrw2Cfg<CO, CO, W, COW, CIWV, NB>;
+// work split <COW, CIWV, NB> and final-kernel width CW of one instance
+template <class I, int COW, int CIWV, int NB, int CW>
+static torch::Tensor conv3x3_wrw2_launch(const torch::Tensor& dy,
+                                         const torch::Tensor& x, int N,
+                                         int H) {
+  using C = Wrw2Cfg<I::CO, I::CI, I::W, COW, CIWV, NB>;
+  // a supertile is 128 positions (64 at W=8) of whole rows of ONE image
+  TORCH_CHECK(N > 0 && H > 0 && H % C::SR == 0,
+              "conv3x3_wrw2: unsupported (N,H)=", N, ",", H);
+  auto dw = conv_empty(x, {I::CO, I::CI, 3, 3});
   const long tiles = (long)N * (H / C::SR);
-  const int cap = conv3x3_wrw2_grid_cap(CO);
+  const int cap = conv3x3_wrw2_grid_cap(I::CO);
   const int RQ = (int)(tiles < cap ? tiles : cap);   // streams = rows/quadrant
   auto part = torch::empty({(long)C::Q * RQ, 9L * 256},
                            x.options().dtype(torch::kFloat));
-  hipLaunchKernelGGL((conv3x3_wrw2_k<CO, CO, W, COW, CIWV, NB>),
-                     dim3(RQ * C::G), dim3(FT_BLOCK), 0, STREAM,
-                     reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
-                     part.data_ptr<float>(), N, H, RQ);
+  hipLaunchKernelGGL((conv3x3_wrw2_k<I::CO, I::CI, I::W, COW, CIWV, NB>),
+                     dim3(RQ * C::G), dim3(FT_BLOCK), 0, STREAM, bf16_ptr(dy),
+                     bf16_ptr(x), part.data_ptr<float>(), N, H, RQ);
   hipLaunchKernelGGL(conv3x3_wrw2_final_k<CW>, dim3(C::Q * (9 * 256 / CW)),
                      dim3(FT_BLOCK), 0, STREAM, part.data_ptr<float>(), RQ,
-                     reinterpret_cast<__hip_bfloat16*>(dw.data_ptr()), CO);
+                     bf16_out(dw), I::CO);
+  return dw;
 }
 
 torch::Tensor conv3x3_wrw2(torch::Tensor dy, torch::Tensor x) {
-  TORCH_CHECK(dy.is_cuda() && x.is_cuda() && dy.dim() == 4 && x.dim() == 4,
-              "conv3x3_wrw2: 4D GPU tensors");
-  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast)
-                  && x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3_wrw2: channels_last only");
-  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16
-                  && x.scalar_type() == torch::kBFloat16,
-              "conv3x3_wrw2: bf16 only");
+  const char* who = "conv3x3_wrw2";
+  conv_check_act(who, "x", x);
   const int N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
+  conv_check_dy(who, dy, N, H, W);
   const int Co = dy.size(1);
-  const bool ok = (Co == Ci) && ((Co == 16 && W == 32) ||
-                                 (Co == 32 && W == 16) ||
-                                 (Co == 64 && W == 8));
-  TORCH_CHECK(ok, "conv3x3_wrw2: unsupported (Co,Ci,W)=", Co, ",", Ci, ",",
-              W);
-  // a supertile is 128 positions (64 at W=8) of whole rows of ONE image
-  TORCH_CHECK(N > 0 && H > 0 && H % ((W == 8 ? 64 : 128) / W) == 0,
-              "conv3x3_wrw2: unsupported (N,H)=", N, ",", H);
-  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W,
-              "conv3x3_wrw2: dy must be [N, Co, H, W]");
-  auto dw = torch::empty(
-      {Co, Ci, 3, 3},
-      x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  // work split <COW, CIWV, NB> and final-kernel width per shape: see the
-  // header of convwrw2.h and the sweep in profiles/wrw2_notes.md
-  if (Co == 16)
-    conv3x3_wrw2_launch<16, 32, 1, 1, 1, 16>(dy, x, dw, N, H);
-  else if (Co == 32)
-    conv3x3_wrw2_launch<32, 16, 2, 1, 1, 32>(dy, x, dw, N, H);
-  else
-    conv3x3_wrw2_launch<64, 8, 2, 2, 1, 32>(dy, x, dw, N, H);
+  torch::Tensor dw;
+  // the splits: header of convwrw2.h and the sweep in profiles/wrw2_notes.md
+  conv_dispatch<1>(who, Ci, Co, W, [&](auto inst) {
+    using I = decltype(inst);
+    if constexpr (I::CO == 16)
+      dw = conv3x3_wrw2_launch<I, 1, 1, 1, 16>(dy, x, N, H);
+    else if constexpr (I::CO == 32)
+      dw = conv3x3_wrw2_launch<I, 2, 1, 1, 32>(dy, x, N, H);
+    else
+      dw = conv3x3_wrw2_launch<I, 2, 2, 1, 32>(dy, x, N, H);
+  });
   return dw;
 }
 
@@ -941,37 +1044,6 @@ torch::Tensor conv3x3_wrw2(torch::Tensor dy, torch::Tensor x) {
 // MFMA direct NHWC 3x3/s1/p1 conv FORWARD with fused BN prologue/epilogue
 // (convfwd.h)
 // ==========================================================================
-// argument checks shared by the convfwd.h launchers: the kernels index
-// every pointer from the activation's sizes alone, so each tensor handed
-// to them is validated here.  Optional arguments are absent when empty.
-static inline bool conv_present(const torch::Tensor& t) {
-  return t.defined() && t.numel() > 0;
-}
-
-// w: [Co, Ci, 3, 3] bf16 channels_last on the GPU (memory [Co][3][3][Ci])
-static inline void conv_check_w(const char* who, const torch::Tensor& w,
-                                int Co, int Ci) {
-  TORCH_CHECK(w.is_cuda() && w.dim() == 4, who, ": w must be 4D on GPU");
-  TORCH_CHECK(w.scalar_type() == torch::kBFloat16, who, ": bf16 only");
-  TORCH_CHECK(w.size(0) == Co && w.size(1) == Ci && w.size(2) == 3 &&
-                  w.size(3) == 3,
-              who, ": w must be [Co, Ci, 3, 3] = [", Co, ", ", Ci,
-              ", 3, 3]");
-  TORCH_CHECK(w.is_contiguous(at::MemoryFormat::ChannelsLast), who,
-              ": w must be channels_last");
-}
-
-// t: bf16 channels_last GPU tensor with exactly ref's sizes
-static inline void conv_check_like(const char* who, const char* name,
-                                   const torch::Tensor& t,
-                                   const torch::Tensor& ref) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16, who, ": ",
-              name, " must be bf16 on GPU");
-  TORCH_CHECK(t.sizes() == ref.sizes() &&
-                  t.is_contiguous(at::MemoryFormat::ChannelsLast),
-              who, ": ", name, " must match ", ref.sizes(),
-              ", channels_last");
-}
 
 // ysum: [grid, Co, 2] fp32 stats partials, or empty
 static inline float* conv_check_ysum(const char* who,
@@ -990,30 +1062,16 @@ torch::Tensor conv3x3_bn_fwd(torch::Tensor x, torch::Tensor w,
                              torch::Tensor ysum, torch::Tensor in_a,
                              torch::Tensor in_b, torch::Tensor res,
                              bool relu_in) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4,
-              "conv3x3_bn_fwd: 4D GPU tensors");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3_bn_fwd: channels_last only");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
-                  w.scalar_type() == torch::kBFloat16,
-              "conv3x3_bn_fwd: bf16 only");
+  const char* who = "conv3x3_bn_fwd";
+  conv_check_act(who, "x", x);
+  conv_check_act(who, "w", w);
   const int N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
   const int Co = w.size(0);
-  const bool ok = (Co == Ci) && ((Co == 16 && W == 32) ||
-                                 (Co == 32 && W == 16) ||
-                                 (Co == 64 && W == 8));
-  TORCH_CHECK(ok, "conv3x3_bn_fwd: unsupported (Co,Ci,W)=",
-              Co, ",", Ci, ",", W);
-  TORCH_CHECK(N > 0 && H > 0 && H % 8 == 0,
-              "conv3x3_bn_fwd: unsupported (N,H)=", N, ",", H);
-  conv_check_w("conv3x3_bn_fwd", w, Co, Ci);
-  auto y = torch::empty(
-      {N, Co, H, W},
-      x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  float* ysp = conv_check_ysum("conv3x3_bn_fwd", ysum,
-                               (long)N * (H / 8) * (Co == 64 ? 2 : 1), Co);
-  TORCH_CHECK(conv_present(in_a) == conv_present(in_b),
-              "conv3x3_bn_fwd: in_a and in_b go together");
+  TORCH_CHECK(N > 0 && H > 0 && H % 8 == 0, who, ": unsupported (N,H)=", N,
+              ",", H);
+  conv_check_w(who, w, Co, Ci);
+  TORCH_CHECK(conv_present(in_a) == conv_present(in_b), who,
+              ": in_a and in_b go together");
   const float* ap = nullptr;
   const float* bp = nullptr;
   if (conv_present(in_a)) {
@@ -1022,51 +1080,35 @@ torch::Tensor conv3x3_bn_fwd(torch::Tensor x, torch::Tensor w,
                     in_b.scalar_type() == torch::kFloat &&
                     in_a.is_contiguous() && in_b.is_contiguous() &&
                     in_a.numel() == Ci && in_b.numel() == Ci,
-                "conv3x3_bn_fwd: in_a/in_b must be fp32 [Ci] on GPU, Ci=",
-                Ci);
+                who, ": in_a/in_b must be fp32 [Ci] on GPU, Ci=", Ci);
     ap = in_a.data_ptr<float>();
     bp = in_b.data_ptr<float>();
   }
   const __hip_bfloat16* rp = nullptr;
   if (conv_present(res)) {
-    conv_check_like("conv3x3_bn_fwd", "res", res, x);
-    rp = reinterpret_cast<const __hip_bfloat16*>(res.data_ptr());
+    conv_check_like(who, "res", res, x.sizes());
+    rp = bf16_ptr(res);
   }
-  const __hip_bfloat16* xp =
-      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
-  const __hip_bfloat16* wp =
-      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
-  __hip_bfloat16* yp = reinterpret_cast<__hip_bfloat16*>(y.data_ptr());
-  const bool fuse = ap != nullptr;
-  const bool hres = rp != nullptr;
-  TORCH_CHECK(!hres || fuse, "conv3x3_bn_fwd: residual needs in_a/in_b");
-#define FT_CONV_LAUNCH(CI_, CO_, COT_, W_, XN_)                            \
-  {                                                                        \
-    const int grid = N * (H / 8) * XN_;                                    \
-    if (fuse && hres)                                                      \
-      hipLaunchKernelGGL((conv3x3_bn_fwd_k<CI_, CO_, COT_, W_, true,       \
-                                           true>),                        \
-                         dim3(grid), dim3(FT_BLOCK), 0, STREAM, xp, wp,    \
-                         yp, ysp, ap, bp, rp, N, H, relu_in ? 1 : 0);      \
-    else if (fuse)                                                         \
-      hipLaunchKernelGGL((conv3x3_bn_fwd_k<CI_, CO_, COT_, W_, true,       \
-                                           false>),                       \
-                         dim3(grid), dim3(FT_BLOCK), 0, STREAM, xp, wp,    \
-                         yp, ysp, ap, bp, rp, N, H, relu_in ? 1 : 0);      \
-    else                                                                   \
-      hipLaunchKernelGGL((conv3x3_bn_fwd_k<CI_, CO_, COT_, W_, false,      \
-                                           false>),                       \
-                         dim3(grid), dim3(FT_BLOCK), 0, STREAM, xp, wp,    \
-                         yp, ysp, ap, bp, rp, N, H, relu_in ? 1 : 0);      \
-  }
-  if (Co == 16) {
-    FT_CONV_LAUNCH(16, 16, 16, 32, 1)
-  } else if (Co == 32) {
-    FT_CONV_LAUNCH(32, 32, 32, 16, 1)
-  } else {
-    FT_CONV_LAUNCH(64, 64, 32, 8, 2)
-  }
-#undef FT_CONV_LAUNCH
+  TORCH_CHECK(!rp || ap, who, ": residual needs in_a/in_b");
+  torch::Tensor y;
+  conv_dispatch<1>(who, Ci, Co, W, [&](auto inst) {
+    using I = decltype(inst);
+    const int grid = N * (H / 8) * I::SPLIT;
+    float* ysp = conv_check_ysum(who, ysum, grid, Co);
+    y = conv_empty(x, {N, Co, H, W});
+    auto launch = [&](auto fuse_in, auto has_res) {
+      hipLaunchKernelGGL(
+          (conv3x3_bn_fwd_k<I::CI, I::CO, I::CO_TILE, I::W,
+                            decltype(fuse_in)::value,
+                            decltype(has_res)::value>),
+          dim3(grid), dim3(FT_BLOCK), 0, STREAM, bf16_ptr(x), bf16_ptr(w),
+          bf16_out(y), ysp, ap, bp, rp, N, H, relu_in ? 1 : 0);
+    };
+    // the three flag pairs the kernel is built for
+    if (rp) launch(std::true_type{}, std::true_type{});
+    else if (ap) launch(std::true_type{}, std::false_type{});
+    else launch(std::false_type{}, std::false_type{});
+  });
   return y;
 }
 
@@ -1075,40 +1117,26 @@ torch::Tensor conv3x3_bn_fwd(torch::Tensor x, torch::Tensor w,
 // ==========================================================================
 torch::Tensor conv3x3s2_bn_fwd(torch::Tensor x, torch::Tensor w,
                                torch::Tensor ysum) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4 &&
-                  x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3s2_bn_fwd: channels_last GPU");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
-                  w.scalar_type() == torch::kBFloat16,
-              "conv3x3s2_bn_fwd: bf16 only");
+  const char* who = "conv3x3s2_bn_fwd";
+  conv_check_act(who, "x", x);
+  conv_check_act(who, "w", w);
   const int N = x.size(0), Ci = x.size(1), HI = x.size(2), WI = x.size(3);
   const int Co = w.size(0);
-  const int H = HI / 2, W = WI / 2;
-  const bool ok = (Co == 2 * Ci) && ((Ci == 16 && WI == 32) ||
-                                     (Ci == 32 && WI == 16));
-  TORCH_CHECK(ok, "conv3x3s2_bn_fwd: unsupported (Ci,Co,WI)=", Ci, ",",
-              Co, ",", WI);
-  TORCH_CHECK(N > 0 && HI > 0 && HI % 16 == 0,
-              "conv3x3s2_bn_fwd: unsupported (N,H_in)=", N, ",", HI);
-  conv_check_w("conv3x3s2_bn_fwd", w, Co, Ci);
-  auto y = torch::empty(
-      {N, Co, H, W},
-      x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int grid = N * (H / 8) * (Co / 32);
-  float* ysp = conv_check_ysum("conv3x3s2_bn_fwd", ysum, grid, Co);
-  const __hip_bfloat16* xp =
-      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
-  const __hip_bfloat16* wp =
-      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
-  __hip_bfloat16* yp = reinterpret_cast<__hip_bfloat16*>(y.data_ptr());
-  if (Ci == 16)
-    hipLaunchKernelGGL((conv3x3_bn_fwd_k<16, 32, 32, 16, false, false, 2>),
-                       dim3(grid), dim3(FT_BLOCK), 0, STREAM, xp, wp, yp,
-                       ysp, nullptr, nullptr, nullptr, N, H, 0);
-  else
-    hipLaunchKernelGGL((conv3x3_bn_fwd_k<32, 64, 32, 8, false, false, 2>),
-                       dim3(grid), dim3(FT_BLOCK), 0, STREAM, xp, wp, yp,
-                       ysp, nullptr, nullptr, nullptr, N, H, 0);
+  const int H = HI / 2;
+  TORCH_CHECK(N > 0 && HI > 0 && HI % 16 == 0, who,
+              ": unsupported (N,H_in)=", N, ",", HI);
+  conv_check_w(who, w, Co, Ci);
+  torch::Tensor y;
+  conv_dispatch<2>(who, Ci, Co, WI, [&](auto inst) {
+    using I = decltype(inst);
+    const int grid = N * (H / 8) * I::SPLIT;
+    float* ysp = conv_check_ysum(who, ysum, grid, Co);
+    y = conv_empty(x, {N, Co, H, I::W});
+    hipLaunchKernelGGL(
+        (conv3x3_bn_fwd_k<I::CI, I::CO, I::CO_TILE, I::W, false, false, 2>),
+        dim3(grid), dim3(FT_BLOCK), 0, STREAM, bf16_ptr(x), bf16_ptr(w),
+        bf16_out(y), ysp, nullptr, nullptr, nullptr, N, H, 0);
+  });
   return y;
 }
 
@@ -1135,22 +1163,11 @@ torch::Tensor conv3x3_bn_act_fwd(torch::Tensor x, torch::Tensor w,
   const char* who = "conv3x3_bn_act_fwd";
   TORCH_CHECK(stride == 1 || stride == 2, who, ": stride must be 1 or 2, got ",
               stride);
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4, who, ": x must be 4D on GPU");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, who, ": bf16 only");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), who,
-              ": channels_last only");
-  TORCH_CHECK(w.dim() == 4, who, ": w must be 4D");
+  conv_check_act(who, "x", x);
+  conv_check_act(who, "w", w);
   const int N = x.size(0), Ci = x.size(1), HI = x.size(2), WI = x.size(3);
   const int Co = w.size(0);
   const int S = (int)stride;
-  bool ok;
-  if (S == 1)
-    ok = (Co == Ci) && ((Co == 16 && WI == 32) || (Co == 32 && WI == 16) ||
-                        (Co == 64 && WI == 8));
-  else
-    ok = (Co == 2 * Ci) && ((Ci == 16 && WI == 32) || (Ci == 32 && WI == 16));
-  TORCH_CHECK(ok, who, ": unsupported (Ci,Co,W)=", Ci, ",", Co, ",", WI,
-              " at stride ", S);
   TORCH_CHECK(N > 0 && HI > 0 && HI % (8 * S) == 0, who,
               ": unsupported (N,H)=", N, ",", HI, " at stride ", S);
   conv_check_w(who, w, Co, Ci);
@@ -1159,46 +1176,27 @@ torch::Tensor conv3x3_bn_act_fwd(torch::Tensor x, torch::Tensor w,
   const float* mp = conv_check_vec(who, "running_mean", running_mean, Co);
   const float* vp = conv_check_vec(who, "running_var", running_var, Co);
   const int H = HI / S, W = WI / S;
-  auto y = torch::empty(
-      {N, Co, H, W},
-      x.options().memory_format(at::MemoryFormat::ChannelsLast));
   const __hip_bfloat16* rp = nullptr;
   if (conv_present(res)) {
-    conv_check_like(who, "res", res, y);   // the OUTPUT shape
-    rp = reinterpret_cast<const __hip_bfloat16*>(res.data_ptr());
+    conv_check_like(who, "res", res, {N, Co, H, W});   // the OUTPUT shape
+    rp = bf16_ptr(res);
   }
-  const __hip_bfloat16* xp =
-      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
-  const __hip_bfloat16* wp =
-      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
-  __hip_bfloat16* yp = reinterpret_cast<__hip_bfloat16*>(y.data_ptr());
   TORCH_CHECK((long)N * (H / 8) * 2 < (1L << 31), who, ": N too large");
-#define FT_CONV_EVAL_LAUNCH(CI_, CO_, COT_, W_, S_)                        \
-  {                                                                        \
-    const int grid = N * (H / 8) * (CO_ / COT_);                           \
-    if (rp != nullptr)                                                     \
-      hipLaunchKernelGGL(                                                  \
-          (conv3x3_bn_act_fwd_k<CI_, CO_, COT_, W_, true, S_>), dim3(grid), \
-          dim3(FT_BLOCK), 0, STREAM, xp, wp, yp, gp, bp, mp, vp, rp,       \
-          (float)eps, N, H, relu ? 1 : 0);                                 \
-    else                                                                   \
-      hipLaunchKernelGGL(                                                  \
-          (conv3x3_bn_act_fwd_k<CI_, CO_, COT_, W_, false, S_>),           \
-          dim3(grid), dim3(FT_BLOCK), 0, STREAM, xp, wp, yp, gp, bp, mp,   \
-          vp, rp, (float)eps, N, H, relu ? 1 : 0);                         \
-  }
-  if (S == 1 && Co == 16) {
-    FT_CONV_EVAL_LAUNCH(16, 16, 16, 32, 1)
-  } else if (S == 1 && Co == 32) {
-    FT_CONV_EVAL_LAUNCH(32, 32, 32, 16, 1)
-  } else if (S == 1) {
-    FT_CONV_EVAL_LAUNCH(64, 64, 32, 8, 1)
-  } else if (Ci == 16) {
-    FT_CONV_EVAL_LAUNCH(16, 32, 32, 16, 2)
-  } else {
-    FT_CONV_EVAL_LAUNCH(32, 64, 32, 8, 2)
-  }
-#undef FT_CONV_EVAL_LAUNCH
+  torch::Tensor y;
+  auto run = [&](auto inst) {
+    using I = decltype(inst);
+    const int grid = N * (H / 8) * I::SPLIT;
+    y = conv_empty(x, {N, Co, H, W});
+    bool_dispatch(rp != nullptr, [&](auto has_res) {
+      hipLaunchKernelGGL(
+          (conv3x3_bn_act_fwd_k<I::CI, I::CO, I::CO_TILE, I::W,
+                                decltype(has_res)::value, I::S>),
+          dim3(grid), dim3(FT_BLOCK), 0, STREAM, bf16_ptr(x), bf16_ptr(w),
+          bf16_out(y), gp, bp, mp, vp, rp, (float)eps, N, H, relu ? 1 : 0);
+    });
+  };
+  if (S == 1) conv_dispatch<1>(who, Ci, Co, WI, run);
+  else conv_dispatch<2>(who, Ci, Co, WI, run);
   return y;
 }
 
@@ -1206,47 +1204,26 @@ torch::Tensor conv3x3_bn_act_fwd(torch::Tensor x, torch::Tensor w,
 // MFMA direct conv backward-data (convfwd.h conv3x3_dgrad_k)
 // ==========================================================================
 torch::Tensor conv3x3_dgrad(torch::Tensor dy, torch::Tensor w) {
-  TORCH_CHECK(dy.is_cuda() && w.is_cuda() && dy.dim() == 4 && w.dim() == 4,
-              "conv3x3_dgrad: 4D GPU tensors");
-  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3_dgrad: channels_last only");
-  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
-                  w.scalar_type() == torch::kBFloat16,
-              "conv3x3_dgrad: bf16 only");
+  const char* who = "conv3x3_dgrad";
+  conv_check_act(who, "dy", dy);
+  conv_check_act(who, "w", w);
   const int N = dy.size(0), Co = dy.size(1), H = dy.size(2),
             W = dy.size(3);
   const int Ci = w.size(1);
-  const bool ok = (Co == Ci) && ((Co == 16 && W == 32) ||
-                                 (Co == 32 && W == 16) ||
-                                 (Co == 64 && W == 8));
-  TORCH_CHECK(ok, "conv3x3_dgrad: unsupported (Co,Ci,W)=", Co, ",", Ci,
-              ",", W);
-  TORCH_CHECK(N > 0 && H > 0 && H % 8 == 0,
-              "conv3x3_dgrad: unsupported (N,H)=", N, ",", H);
-  conv_check_w("conv3x3_dgrad", w, Co, Ci);
-  auto dx = torch::empty(
-      {N, Ci, H, W},
-      dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const __hip_bfloat16* dyp =
-      reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr());
-  const __hip_bfloat16* wp =
-      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
-  __hip_bfloat16* dxp = reinterpret_cast<__hip_bfloat16*>(dx.data_ptr());
-  if (Co == 16)
-    hipLaunchKernelGGL((conv3x3_dgrad_k<16, 16, 16, 32, false>),
-                       dim3(N * (H / 8)), dim3(FT_BLOCK), 0, STREAM, dyp,
-                       wp, dxp, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, N, H, 0);
-  else if (Co == 32)
-    hipLaunchKernelGGL((conv3x3_dgrad_k<32, 32, 32, 16, false>),
-                       dim3(N * (H / 8)), dim3(FT_BLOCK), 0, STREAM, dyp,
-                       wp, dxp, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, N, H, 0);
-  else
-    hipLaunchKernelGGL((conv3x3_dgrad_k<64, 64, 32, 8, false>),
-                       dim3(N * (H / 8) * 2), dim3(FT_BLOCK), 0, STREAM,
-                       dyp, wp, dxp, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, N, H, 0);
+  TORCH_CHECK(N > 0 && H > 0 && H % 8 == 0, who, ": unsupported (N,H)=", N,
+              ",", H);
+  conv_check_w(who, w, Co, Ci);
+  torch::Tensor dx;
+  // the output tile of the mirror kernel is a CI tile; Ci == Co here
+  conv_dispatch<1>(who, Ci, Co, W, [&](auto inst) {
+    using I = decltype(inst);
+    dx = conv_empty(dy, {N, Ci, H, W});
+    hipLaunchKernelGGL(
+        (conv3x3_dgrad_k<I::CI, I::CO, I::CO_TILE, I::W, false>),
+        dim3(N * (H / 8) * I::SPLIT), dim3(FT_BLOCK), 0, STREAM,
+        bf16_ptr(dy), bf16_ptr(w), bf16_out(dx), nullptr, nullptr, nullptr,
+        nullptr, nullptr, N, H, 0);
+  });
   return dx;
 }
 
@@ -1257,121 +1234,65 @@ torch::Tensor conv3x3_dgrad(torch::Tensor dy, torch::Tensor w) {
 std::vector<torch::Tensor> conv3x3_dgrad_bn(
     torch::Tensor dz, torch::Tensor w, torch::Tensor xbn, torch::Tensor z,
     torch::Tensor coefs, bool relu, torch::Tensor dres) {
-  TORCH_CHECK(dz.is_cuda() && dz.dim() == 4 && w.is_cuda() &&
-                  w.dim() == 4 &&
-                  dz.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3_dgrad_bn: channels_last GPU dz");
-  TORCH_CHECK(dz.scalar_type() == torch::kBFloat16 &&
-                  w.scalar_type() == torch::kBFloat16,
-              "conv3x3_dgrad_bn: bf16 only");
+  const char* who = "conv3x3_dgrad_bn";
+  conv_check_act(who, "dz", dz);
+  conv_check_act(who, "w", w);
   const int N = dz.size(0), Co = dz.size(1), H = dz.size(2),
             W = dz.size(3);
   const int Ci = w.size(1);
-  const bool ok = (Co == Ci) && ((Co == 16 && W == 32) ||
-                                 (Co == 32 && W == 16) ||
-                                 (Co == 64 && W == 8));
-  TORCH_CHECK(ok && N > 0 && H > 0 && H % 8 == 0,
-              "conv3x3_dgrad_bn: unsupported shape");
-  conv_check_w("conv3x3_dgrad_bn", w, Co, Ci);
-  conv_check_like("conv3x3_dgrad_bn", "xbn", xbn, dz);
-  conv_check_like("conv3x3_dgrad_bn", "z", z, dz);
+  TORCH_CHECK(N > 0 && H > 0 && H % 8 == 0, who, ": unsupported (N,H)=", N,
+              ",", H);
+  conv_check_w(who, w, Co, Ci);
+  conv_check_like(who, "xbn", xbn, dz.sizes());
+  conv_check_like(who, "z", z, dz.sizes());
   TORCH_CHECK(coefs.numel() == 3 * Co && coefs.is_cuda() &&
                   coefs.scalar_type() == torch::kFloat &&
                   coefs.is_contiguous(),
-              "conv3x3_dgrad_bn: coefs must be fp32 [3, Co]");
-  auto dx = torch::empty(
-      {N, Ci, H, W},
-      dz.options().memory_format(at::MemoryFormat::ChannelsLast));
-  auto dyc = torch::empty_like(dz);
+              who, ": coefs must be fp32 [3, Co]");
   const bool want_dres = conv_present(dres);
-  if (want_dres) conv_check_like("conv3x3_dgrad_bn", "dres", dres, dz);
-  const __hip_bfloat16* dzp =
-      reinterpret_cast<const __hip_bfloat16*>(dz.data_ptr());
-  const __hip_bfloat16* wp =
-      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
-  const __hip_bfloat16* xp =
-      reinterpret_cast<const __hip_bfloat16*>(xbn.data_ptr());
-  const __hip_bfloat16* zp =
-      reinterpret_cast<const __hip_bfloat16*>(z.data_ptr());
-  __hip_bfloat16* dxp = reinterpret_cast<__hip_bfloat16*>(dx.data_ptr());
-  __hip_bfloat16* dycp = reinterpret_cast<__hip_bfloat16*>(dyc.data_ptr());
-  __hip_bfloat16* drp = want_dres
-      ? reinterpret_cast<__hip_bfloat16*>(dres.data_ptr()) : nullptr;
-  const float* cp = coefs.data_ptr<float>();
-  const int rl = relu ? 1 : 0;
-#define FT_DG_LAUNCH(CI_, CO_, CT_, W_, XN_)                              \
-  {                                                                       \
-    if (want_dres)                                                        \
-      hipLaunchKernelGGL((conv3x3_dgrad_k<CI_, CO_, CT_, W_, true,        \
-                                          true>),                        \
-                         dim3(N * (H / 8) * XN_), dim3(FT_BLOCK), 0,      \
-                         STREAM, dzp, wp, dxp, xp, zp, cp, dycp, drp, N,  \
-                         H, rl);                                          \
-    else                                                                  \
-      hipLaunchKernelGGL((conv3x3_dgrad_k<CI_, CO_, CT_, W_, true,        \
-                                          false>),                       \
-                         dim3(N * (H / 8) * XN_), dim3(FT_BLOCK), 0,      \
-                         STREAM, dzp, wp, dxp, xp, zp, cp, dycp, drp, N,  \
-                         H, rl);                                          \
-  }
-  if (Co == 16) {
-    FT_DG_LAUNCH(16, 16, 16, 32, 1)
-  } else if (Co == 32) {
-    FT_DG_LAUNCH(32, 32, 32, 16, 1)
-  } else {
-    FT_DG_LAUNCH(64, 64, 32, 8, 2)
-  }
-#undef FT_DG_LAUNCH
+  if (want_dres) conv_check_like(who, "dres", dres, dz.sizes());
+  torch::Tensor dx, dyc;
+  conv_dispatch<1>(who, Ci, Co, W, [&](auto inst) {
+    using I = decltype(inst);
+    dx = conv_empty(dz, {N, Ci, H, W});
+    dyc = torch::empty_like(dz);
+    bool_dispatch(want_dres, [&](auto has_dres) {
+      hipLaunchKernelGGL(
+          (conv3x3_dgrad_k<I::CI, I::CO, I::CO_TILE, I::W, true,
+                           decltype(has_dres)::value>),
+          dim3(N * (H / 8) * I::SPLIT), dim3(FT_BLOCK), 0, STREAM,
+          bf16_ptr(dz), bf16_ptr(w), bf16_out(dx), bf16_ptr(xbn), bf16_ptr(z),
+          coefs.data_ptr<float>(), bf16_out(dyc),
+          want_dres ? bf16_out(dres) : nullptr, N, H, relu ? 1 : 0);
+    });
+  });
   return {dx, dyc};
 }
 
 // ==========================================================================
 // MFMA backward of the 3x3/s2 transition convs (convs2bwd.h)
 // ==========================================================================
-static inline void s2bwd_check(const char* who, const torch::Tensor& dy,
-                               const torch::Tensor& other, int Ci, int Co,
-                               int HI, int WI) {
-  TORCH_CHECK(dy.is_cuda() && other.is_cuda() && dy.dim() == 4 &&
-                  other.dim() == 4,
-              who, ": 4D GPU tensors");
-  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                  other.is_contiguous(at::MemoryFormat::ChannelsLast),
-              who, ": channels_last only");
-  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
-                  other.scalar_type() == torch::kBFloat16,
-              who, ": bf16 only");
-  const bool ok = (Co == 2 * Ci) && ((Ci == 16 && WI == 32) ||
-                                     (Ci == 32 && WI == 16));
-  TORCH_CHECK(ok, who, ": unsupported (Ci,Co,WI)=", Ci, ",", Co, ",", WI);
-  TORCH_CHECK(HI > 0 && HI % 16 == 0, who, ": H_in % 16 != 0");
-}
-
 torch::Tensor conv3x3s2_dgrad(torch::Tensor dy, torch::Tensor w) {
-  TORCH_CHECK(dy.dim() == 4 && w.dim() == 4,
-              "conv3x3s2_dgrad: 4D GPU tensors");
+  const char* who = "conv3x3s2_dgrad";
+  conv_check_act(who, "dy", dy);
+  conv_check_act(who, "w", w);
   const int N = dy.size(0), Co = dy.size(1);
   const int HI = dy.size(2) * 2, WI = dy.size(3) * 2;
   const int Ci = w.size(1);
-  s2bwd_check("conv3x3s2_dgrad", dy, w, Ci, Co, HI, WI);
-  TORCH_CHECK(w.size(0) == Co && w.size(2) == 3 && w.size(3) == 3,
-              "conv3x3s2_dgrad: w must be [Co, Ci, 3, 3]");
-  auto dx = torch::empty(
-      {N, Ci, HI, WI},
-      dy.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const __hip_bfloat16* dyp =
-      reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr());
-  const __hip_bfloat16* wp =
-      reinterpret_cast<const __hip_bfloat16*>(w.data_ptr());
-  __hip_bfloat16* dxp = reinterpret_cast<__hip_bfloat16*>(dx.data_ptr());
-  if (N == 0) return dx;
-  if (Ci == 16)   // 8 input rows per workgroup
-    hipLaunchKernelGGL((conv3x3s2_dgrad_k<16, 32, 16, 32>),
-                       dim3(N * (HI / 8)), dim3(FT_BLOCK), 0, STREAM, dyp,
-                       wp, dxp, N, HI);
-  else            // 16 input rows x 2 ci tiles
-    hipLaunchKernelGGL((conv3x3s2_dgrad_k<32, 64, 16, 16>),
-                       dim3(N * (HI / 16) * 2), dim3(FT_BLOCK), 0, STREAM,
-                       dyp, wp, dxp, N, HI);
+  TORCH_CHECK(HI > 0 && HI % 16 == 0, who, ": H_in % 16 != 0");
+  conv_check_w(who, w, Co, Ci);
+  torch::Tensor dx;
+  conv_dispatch<2>(who, Ci, Co, WI, [&](auto inst) {
+    using I = decltype(inst);
+    // a workgroup: 256 input pixels (whole rows) x 16 input channels
+    constexpr int CI_TILE = 16, R = 256 / I::W_IN;
+    dx = conv_empty(dy, {N, Ci, HI, WI});
+    if (N == 0) return;
+    hipLaunchKernelGGL((conv3x3s2_dgrad_k<I::CI, I::CO, CI_TILE, I::W_IN>),
+                       dim3(N * (HI / R) * (I::CI / CI_TILE)),
+                       dim3(FT_BLOCK), 0, STREAM, bf16_ptr(dy), bf16_ptr(w),
+                       bf16_out(dx), N, HI);
+  });
   return dx;
 }
 
@@ -1386,107 +1307,72 @@ int conv3x3s2_wrw_grid_cap(int Ci) {
 }
 
 torch::Tensor conv3x3s2_wrw(torch::Tensor dy, torch::Tensor x) {
-  TORCH_CHECK(dy.dim() == 4 && x.dim() == 4,
-              "conv3x3s2_wrw: 4D GPU tensors");
+  const char* who = "conv3x3s2_wrw";
+  conv_check_act(who, "x", x);
   const int N = x.size(0), Ci = x.size(1), HI = x.size(2), WI = x.size(3);
+  TORCH_CHECK(N > 0 && HI > 0 && HI % 16 == 0, who,
+              ": unsupported (N,H_in)=", N, ",", HI);
+  conv_check_dy(who, dy, N, HI / 2, WI / 2);
   const int Co = dy.size(1);
-  s2bwd_check("conv3x3s2_wrw", dy, x, Ci, Co, HI, WI);
-  TORCH_CHECK(dy.size(0) == N && dy.size(2) * 2 == HI &&
-                  dy.size(3) * 2 == WI,
-              "conv3x3s2_wrw: dy must be [N, Co, H_in/2, W_in/2]");
-  auto f32 = x.options().dtype(torch::kFloat);
-  auto dw = torch::empty(
-      {Co, Ci, 3, 3},
-      x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(N > 0, "conv3x3s2_wrw: empty batch");
-  const __hip_bfloat16* dyp =
-      reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr());
-  const __hip_bfloat16* xp =
-      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
-  const long tiles = (long)N * (HI / 16);          // 8 output rows each
-  const int cap = conv3x3s2_wrw_grid_cap(Ci);
-  const int nblk = (int)(tiles < cap ? tiles : cap);
-  const int Q = (Co / 16) * (Ci / 16);
-  const int RQ = nblk;                             // rows per quadrant
-  auto part = torch::empty({(long)Q * RQ, 9L * 256}, f32);
-  if (Ci == 16)
-    hipLaunchKernelGGL((conv3x3s2_wrw_k<32, 16, 32>), dim3(nblk),
-                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
+  torch::Tensor dw;
+  conv_dispatch<2>(who, Ci, Co, WI, [&](auto inst) {
+    using I = decltype(inst);
+    constexpr int Q = (I::CO / 16) * (I::CI / 16);
+    dw = conv_empty(x, {Co, Ci, 3, 3});
+    const long tiles = (long)N * (HI / 16);        // 8 output rows each
+    const int cap = conv3x3s2_wrw_grid_cap(Ci);
+    const int RQ = (int)(tiles < cap ? tiles : cap);   // rows per quadrant
+    auto part = torch::empty({(long)Q * RQ, 9L * 256},
+                             x.options().dtype(torch::kFloat));
+    hipLaunchKernelGGL((conv3x3s2_wrw_k<I::CO, I::CI, I::W_IN>), dim3(RQ),
+                       dim3(FT_BLOCK), 0, STREAM, bf16_ptr(dy), bf16_ptr(x),
                        part.data_ptr<float>(), N, HI, RQ);
-  else
-    hipLaunchKernelGGL((conv3x3s2_wrw_k<64, 32, 16>), dim3(nblk),
-                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
-                       part.data_ptr<float>(), N, HI, RQ);
-  hipLaunchKernelGGL(conv3x3_wrw2_final_k<32>, dim3(Q * 72), dim3(FT_BLOCK), 0,
-                     STREAM, part.data_ptr<float>(), RQ,
-                     reinterpret_cast<__hip_bfloat16*>(dw.data_ptr()), Ci);
+    hipLaunchKernelGGL(conv3x3_wrw2_final_k<32>, dim3(Q * 72),
+                       dim3(FT_BLOCK), 0, STREAM, part.data_ptr<float>(), RQ,
+                       bf16_out(dw), Ci);
+  });
   return dw;
 }
-
 
 // ==========================================================================
 // MFMA 3x3/s1/p1 NHWC bf16 conv weight gradient (convwrw.h)
 // ==========================================================================
 torch::Tensor conv3x3_wrw(torch::Tensor dy, torch::Tensor x) {
-  TORCH_CHECK(dy.is_cuda() && x.is_cuda() && dy.dim() == 4 && x.dim() == 4,
-              "conv3x3_wrw: 4D GPU tensors");
-  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast)
-                  && x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv3x3_wrw: channels_last only");
-  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16
-                  && x.scalar_type() == torch::kBFloat16,
-              "conv3x3_wrw: bf16 only");
+  const char* who = "conv3x3_wrw";
+  conv_check_act(who, "x", x);
   const int N = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3);
+  conv_check_dy(who, dy, N, H, W);
   const int Co = dy.size(1);
-  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W,
-              "conv3x3_wrw: stride-1 same-shape only");
-  const bool ok = (Co == Ci) && ((Co == 16 && W == 32) ||
-                                 (Co == 32 && W == 16) ||
-                                 (Co == 64 && W == 8));
-  TORCH_CHECK(ok, "conv3x3_wrw: unsupported (Co,Ci,W)=", Co, ",", Ci, ",", W);
-  const int R = 32 / W;
-  TORCH_CHECK(H % R == 0, "conv3x3_wrw: H % (32/W) != 0");
-  const long tiles = (long)N * (H / R);
-  auto f32 = x.options().dtype(torch::kFloat);
   static const int cap1 = ft_env_int("FT_WRW_NBLK1", 256);
   static const int capq = ft_env_int("FT_WRW_NBLKQ", 128);
-  int nblk, groups;
-  if (Co == 16) {  // Q==1: 4 independent tile streams per block
-    groups = 4;
-    long b = (tiles + 4 * 4 - 1) / (4 * 4);  // >=4 tiles per stream
-    nblk = (int)(b < 1 ? 1 : (b > cap1 ? cap1 : b));
-  } else {
-    groups = 1;
-    long b = tiles > capq ? capq : tiles;
-    nblk = (int)(b < 1 ? 1 : b);
-  }
-  const long rows = (long)nblk * groups;
-  auto part = torch::empty({rows, (long)9 * Co * Ci}, f32);
-  auto dw = torch::empty(
-      {Co, Ci, 3, 3},
-      x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const __hip_bfloat16* dyp =
-      reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr());
-  const __hip_bfloat16* xp =
-      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
-  if (Co == 16)
-    hipLaunchKernelGGL((conv3x3_wrw_k<16, 16, 32>), dim3(nblk),
-                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
+  torch::Tensor dw;
+  conv_dispatch<1>(who, Ci, Co, W, [&](auto inst) {
+    using I = decltype(inst);
+    constexpr int R = 32 / I::W;   // image rows per 32-position K-tile
+    TORCH_CHECK(H % R == 0, who, ": H % (32/W) != 0");
+    const long tiles = (long)N * (H / R);
+    int nblk, groups;
+    if (I::CO == 16) {  // Q==1: 4 independent tile streams per block
+      groups = 4;
+      long b = (tiles + 4 * 4 - 1) / (4 * 4);  // >=4 tiles per stream
+      nblk = (int)(b < 1 ? 1 : (b > cap1 ? cap1 : b));
+    } else {
+      groups = 1;
+      long b = tiles > capq ? capq : tiles;
+      nblk = (int)(b < 1 ? 1 : b);
+    }
+    const long rows = (long)nblk * groups;
+    auto part = torch::empty({rows, (long)9 * Co * Ci},
+                             x.options().dtype(torch::kFloat));
+    dw = conv_empty(x, {Co, Ci, 3, 3});
+    hipLaunchKernelGGL((conv3x3_wrw_k<I::CO, I::CI, I::W>), dim3(nblk),
+                       dim3(FT_BLOCK), 0, STREAM, bf16_ptr(dy), bf16_ptr(x),
                        part.data_ptr<float>(), N, H);
-  else if (Co == 32)
-    hipLaunchKernelGGL((conv3x3_wrw_k<32, 32, 16>), dim3(nblk),
-                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
-                       part.data_ptr<float>(), N, H);
-  else
-    hipLaunchKernelGGL((conv3x3_wrw_k<64, 64, 8>), dim3(nblk),
-                       dim3(FT_BLOCK), 0, STREAM, dyp, xp,
-                       part.data_ptr<float>(), N, H);
-  const int wn = Co * 9 * Ci;
-  hipLaunchKernelGGL(conv3x3_wrw_final_k, dim3((wn + 63) / 64),
-                     dim3(FT_BLOCK), 0, STREAM, part.data_ptr<float>(),
-                     rows, wn,
-                     reinterpret_cast<__hip_bfloat16*>(dw.data_ptr()), Co,
-                     Ci);
+    const int wn = Co * 9 * Ci;
+    hipLaunchKernelGGL(conv3x3_wrw_final_k, dim3((wn + 63) / 64),
+                       dim3(FT_BLOCK), 0, STREAM, part.data_ptr<float>(),
+                       rows, wn, bf16_out(dw), Co, Ci);
+  });
   return dw;
 }
 
@@ -1499,9 +1385,7 @@ torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
                   && B.numel() == 32 * 16, "probe expects A[16,32] B[32,16] bf16");
   auto D = torch::empty({16, 16}, A.options().dtype(torch::kFloat));
   hipLaunchKernelGGL(mfma_probe_gemm, dim3(1), dim3(64), 0, STREAM,
-                     reinterpret_cast<const __hip_bfloat16*>(A.data_ptr()),
-                     reinterpret_cast<const __hip_bfloat16*>(B.data_ptr()),
-                     D.data_ptr<float>());
+                     bf16_ptr(A), bf16_ptr(B), D.data_ptr<float>());
   return D;
 }
 
