@@ -50,6 +50,10 @@ def main(args):
 
 
 def _dispatch(args):
+    if args.federated and args.clients_per_rank > 1:
+        # unsupported algorithms raise before anything is built or trained
+        from fedtorch_amd.trainings.packed import check_packed_supported
+        check_packed_supported(args)
     client = Client(args, dist.get_rank())
     client.initialize()
     client.initialize_dataset()
@@ -57,7 +61,8 @@ def _dispatch(args):
     client.gen_aux_models()
     if args.federated and args.clients_per_rank > 1:
         # virtual-client packing: C clients per GPU rank, replicas resident
-        # in HBM (fedavg / DRFA-over-fedavg).
+        # in HBM (fedavg / fedprox / scaffold / dense fedgate, each
+        # optionally under DRFA).
         from fedtorch_amd.parallel.multiclient import ClientPack
         from fedtorch_amd.trainings.packed import \
             train_and_validate_federated_packed

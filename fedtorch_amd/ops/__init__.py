@@ -242,6 +242,38 @@ def multi_diff_accumulate(server, replicas, weights, out):
               out=out)
 
 
+def multi_delta_update(delta, server, agg, replicas, inv):
+    """delta[c] += (server - agg - replicas[c]) * inv[c] for every row with
+    inv[c] != 0 (the other rows are neither read nor written) — `delta_update`
+    over the [C, N] rows of the packed clients in ONE pass; inv: [C] fp32,
+    1 / (lr_c tau_c) or 0."""
+    if _use_hip(delta, server, agg, replicas):
+        return _C.multi_delta_update(delta, server, agg, replicas, inv)
+    for c, coef in enumerate(inv.tolist()):
+        if coef != 0.0:
+            delta[c].add_(server - agg - replicas[c], alpha=coef)
+
+
+def multi_scaffold_control_update(ctrl, ctrl_server, server, replicas, inv,
+                                  weights, out):
+    """For every row with inv[c] != 0, in client order:
+    c+ = ctrl[c] - ctrl_server + (server - replicas[c]) * inv[c],
+    out += weights[c] * (c+ - ctrl[c]), ctrl[c] = c+ ; out starts from zero.
+    `scaffold_control_update` + the weighted control delta over the [C, N]
+    rows of the packed clients in ONE pass; rows with inv[c] == 0 are left
+    untouched and contribute nothing."""
+    if _use_hip(ctrl, ctrl_server, server, replicas, out):
+        return _C.multi_scaffold_control_update(ctrl, ctrl_server, server,
+                                                replicas, inv, weights, out)
+    out.zero_()
+    for c, (coef, w) in enumerate(zip(inv.tolist(), weights.tolist())):
+        if coef == 0.0:
+            continue
+        new = (ctrl[c] - ctrl_server).add_(server - replicas[c], alpha=coef)
+        out.add_(new - ctrl[c], alpha=w)
+        ctrl[c].copy_(new)
+
+
 def fedadam_normalize(g, seg, v, beta, tau):
     """FedAdam server normalizer (reference `federated/fedavg.py:81-85`,
     arXiv:2003.00295): per-parameter-tensor v_p = beta*v_p +
@@ -310,7 +342,9 @@ def linear_round_max_floats(uses_momentum):
 
 def linear_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
                         mom_init, snap, k_cut, *, w_off, b_off, K, loss_kind,
-                        weight_decay, momentum, dampening, nesterov):
+                        weight_decay, momentum, dampening, nesterov,
+                        delta=None, ctrl_server=None, ctrl_client=None,
+                        prox_mu=0.0):
     """All local SGD steps of a round, for every packed client of a linear
     model, in one call.
 
@@ -322,10 +356,21 @@ def linear_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
     (1-based), written when 1 <= k_cut <= steps[c].  weight [K, F] sits at
     `w_off`, bias [K] at `b_off` of the arena; every other element is copied
     through.  loss_kind 0 = softmax-CE (mean), 1 = MSE (mean, K == 1).
-    The update is the local branch of `fused_sgd_step`.  in_mom / mom_init
+    The update is the local branch of `fused_sgd_step`, with its gradient
+    corrections: delta [C, N] (d -= delta[c]), or the pair ctrl_server [N] /
+    ctrl_client [C, N] (d += ctrl_server - ctrl_client[c]), and prox_mu
+    (d += prox_mu * (p - server)).  Only the weight and bias elements of the
+    correction rows of clients with steps > 0 are read.  in_mom / mom_init
     are touched only when momentum != 0.  Returns loss [C, T]: the mean loss
     of each executed step, 0 elsewhere."""
     dev = X.device
+    if (ctrl_server is None) != (ctrl_client is None):
+        raise RuntimeError('linear_local_rounds: ctrl_server and ctrl_client '
+                           'come as a pair')
+    if delta is not None and ctrl_server is not None:
+        raise RuntimeError('linear_local_rounds: delta and a control pair '
+                           'together are not supported (one correction '
+                           'vector per client)')
     if in_mom is None:
         in_mom = torch.empty(0, device=dev)
     if snap is None:
@@ -335,13 +380,20 @@ def linear_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
             X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap,
             int(k_cut), int(w_off), int(b_off), int(K), int(loss_kind),
             float(weight_decay), float(momentum), float(dampening),
-            bool(nesterov))
+            bool(nesterov),
+            delta if delta is not None else torch.empty(0, device=dev),
+            ctrl_server if ctrl_server is not None
+            else torch.empty(0, device=dev),
+            ctrl_client if ctrl_client is not None
+            else torch.empty(0, device=dev),
+            float(prox_mu))
 
     # eager twin: a per-client, per-step loop; the gradients come from
     # autograd over F.linear + the loss module's functional, the update from
     # the fused-SGD twin above over the whole row — the ops of the packed
     # slot loop, in its order.  Pad gaps (zero in a real arena, where the
-    # whole-row update leaves them zero) are put back afterwards.
+    # whole-row update leaves them zero) are put back afterwards; those of
+    # the correction rows are masked, never used.
     import torch.nn.functional as Fn
     C, T, _B = idx.shape
     Fdim = X.shape[1]
@@ -353,11 +405,19 @@ def linear_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
     gap = torch.ones_like(server, dtype=torch.bool)
     gap[w_off:w_off + nw] = False
     gap[b_off:b_off + K] = False
+    zero = torch.zeros_like(server)
+    live = lambda t: torch.where(gap, zero, t)  # noqa: E731
     for c in range(C):
         if n_steps[c] <= 0:
             continue
         p = server.clone()
         grad = torch.zeros_like(p)
+        corr = dict(prox_mu=prox_mu, server=server if prox_mu != 0 else None)
+        if delta is not None:
+            corr['delta'] = live(delta[c])
+        if ctrl_server is not None:
+            corr.update(ctrl_server=live(ctrl_server),
+                        ctrl_client=live(ctrl_client[c]))
         mom_gaps = in_mom[c][gap].clone() if use_mom else None
         for s in range(n_steps[c]):
             if snap.numel() and s + 1 == k_cut:
@@ -385,7 +445,7 @@ def linear_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
                 apply_lr=True, apply_in_momentum=use_mom,
                 apply_out_momentum=False,
                 in_buf=in_mom[c] if use_mom else None,
-                first_in=use_mom and not inits[c])
+                first_in=use_mom and not inits[c], **corr)
             if use_mom:
                 inits[c] = 1
         replicas[c].copy_(torch.where(gap, server, p))

@@ -11,7 +11,9 @@
 //       loss[c, s] = mean CE(logits, y)   (loss_kind 0)
 //                  = mean (logits - y)^2  (loss_kind 1, K == 1)
 //       dW = dlogits^T x,  db = sum_rows dlogits
-//       d = g + wd p ; first use: buf = d, else buf = m buf + (1 - damp) d
+//       d = g ; [delta] d -= delta[c] ; [control pair] d += c - c_c[c] ;
+//       [prox_mu] d += mu (p - server)   -- fused_sgd_step's corrections
+//       d += wd p ; first use: buf = d, else buf = m buf + (1 - damp) d
 //       d = nesterov ? d + m buf : buf ; p -= lr[c, s] d
 //     replicas[c] <- parameters (pad gaps copied from server)
 //     in_mom[c]   <- buf, mom_init[c] <- 1            (with momentum only)
@@ -33,7 +35,13 @@
 //   backward  thread t owns features f = t, t+256, ... (f = F: the bias):
 //             loops over the rows IN ORDER, re-reads x[row][f] (an L2 hit),
 //             takes dlogits as an LDS broadcast and applies the SGD update
-//             to its own P[f][.] in LDS.
+//             to its own P[f][.] in LDS.  A gradient correction is constant
+//             over the round and only its owner thread needs it, so it stays
+//             in global memory: the K values of the feature (elements
+//             k F + f, coalesced across threads for each k; the bias takes
+//             b_off + k) are loaded ahead of the row loop, whose B re-reads
+//             of x cover their latency.  The LDS image is the same with and
+//             without a correction.
 //
 // No atomics; every summation order is fixed by (F, K, B), so two runs are
 // bit-identical.  No host reads, no synchronisation: capture-safe.  Padding
@@ -47,13 +55,20 @@
 // floats of LDS: the kernel declares 159 KiB statically, which a single
 // workgroup can get on gfx950 (one workgroup per CU).  K is a template
 // parameter (16 instantiations), so the k loops unroll without guards.
+// A correction adds no limit: it is never staged in LDS.  Its rows are only
+// read for clients with steps > 0, and only at weight and bias elements.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "common.h"
 
 #define LINROUND_THREADS 256
 #define LINROUND_MAXK 16
 #define LINROUND_LDS_FLOATS 40704  // floats: 159 KiB of the CU's 160 KiB
+// gradient corrections of a round (LinRoundArgs.corr, the same in all blocks)
+#define LINROUND_DELTA 1
+#define LINROUND_CTRL 2
+#define LINROUND_PROX 4
 
 // wave64 sum in a fixed order, the total lands in lane 0
 __device__ __forceinline__ float linround_wave_sum(float v) {
@@ -75,10 +90,14 @@ struct LinRoundArgs {
   int* mom_init;         // [C]
   float* snap;           // [C, N] or null
   float* loss;           // [C, T]
+  const float* corr_rows;  // [C, N] or null: delta (d -= delta[c]) or, with
+  const float* ctrl_s;     // ctrl_s [N], the client controls (d += c - c_c[c])
   int M, F, B, T;
   int N, w_off, b_off;   // the arena and the offsets of weight and bias
   int k_cut, use_mom, nesterov;
   float wd, mom, omd;    // omd = 1 - dampening
+  float prox_mu;         // != 0: d += prox_mu (p - server)
+  int corr;              // LINROUND_DELTA | _CTRL | _PROX, 0: no correction
 };
 
 // LDS element of arena element i, or -1 for a pad gap
@@ -122,6 +141,11 @@ linear_round_k(const LinRoundArgs a) {
   float* sp = a.snap ? a.snap + (long)c * a.N + tid : nullptr;
   float* lo = a.loss + (long)c * a.T + tid;   // used by thread 0 alone
   int* mi = a.mom_init + c + tid;            // likewise
+  // the correction's rows likewise: the kernel has no scalar register to
+  // spare, and a per-thread base lives in a vector register
+  const float* cr = a.corr ? a.corr_rows + (long)c * a.N + tid : nullptr;
+  const float* cs = a.corr ? a.ctrl_s + tid : nullptr;
+  const int ow = a.w_off - tid, ob = a.b_off - tid;  // arena offsets likewise
   const bool had_mom = a.use_mom && a.mom_init[c] != 0;
 
   // parameters (and momentum) in; pad gaps of the arena pass through
@@ -220,34 +244,69 @@ linear_round_k(const LinRoundArgs a) {
     }
 
     // ---- backward + SGD: one thread per feature (f == F: the bias) -----
-    for (int f = tid; f <= F; f += LINROUND_THREADS) {
-      const bool isb = f == F;
-      const float* xc = a.X + (isb ? 0 : f);
-      float g[K];
+    // Two copies of the phase, chosen by the block-uniform a.corr: without a
+    // correction the code, and so the arithmetic and the registers of the
+    // row loop, are the ones of a kernel that knows no correction.
+    auto backward = [&](auto with_corr) {
+      constexpr bool CORR = decltype(with_corr)::value;
+      for (int f = tid; f <= F; f += LINROUND_THREADS) {
+        const bool isb = f == F;
+        const float* xc = a.X + (isb ? 0 : f);
+        float g[K];
 #pragma unroll
-      for (int k = 0; k < K; ++k) g[k] = 0.f;
-      for (int b = 0; b < B; ++b) {
-        const int r = is[b];
-        const float t = xc[(long)(r < 0 ? 0 : r) * F];
-        const float xv = r < 0 ? 0.f : (isb ? 1.f : t);
-        const float* zb = zs + b * K;
+        for (int k = 0; k < K; ++k) g[k] = 0.f;
+        // the correction of this feature: issued here, used after the rows
+        float cv[K], sv[K];
+        if (CORR) {
+          // element of (f, k) relative to the per-thread bases: o0 + k es
+          const int o0 = isb ? ob : ow + f;
+          const int es = isb ? 1 : F;
 #pragma unroll
-        for (int k = 0; k < K; ++k) g[k] = fmaf(zb[k], xv, g[k]);
-      }
-      float* pf = Ps + f * KS;
-      float* mf = Ms + f * KS;
+          for (int k = 0; k < K; ++k) cv[k] = sv[k] = 0.f;
+          if (a.corr & LINROUND_DELTA) {
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const float p = pf[k];
-        float d = fmaf(a.wd, p, g[k]);
-        if (a.use_mom) {
-          const float bu = fmaf(mom, mf[k], omd * d);
-          mf[k] = bu;
-          d = a.nesterov ? fmaf(a.mom, bu, d) : bu;
+            for (int k = 0; k < K; ++k) cv[k] = cr[o0 + k * es];
+          } else if (a.corr & LINROUND_CTRL) {
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+              cv[k] = cs[o0 + k * es] - cr[o0 + k * es];
+          }
+          if (a.corr & LINROUND_PROX) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) sv[k] = srv[o0 + k * es];
+          }
         }
-        pf[k] = fmaf(-lr, d, p);
+        for (int b = 0; b < B; ++b) {
+          const int r = is[b];
+          const float t = xc[(long)(r < 0 ? 0 : r) * F];
+          const float xv = r < 0 ? 0.f : (isb ? 1.f : t);
+          const float* zb = zs + b * K;
+#pragma unroll
+          for (int k = 0; k < K; ++k) g[k] = fmaf(zb[k], xv, g[k]);
+        }
+        float* pf = Ps + f * KS;
+        float* mf = Ms + f * KS;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float p = pf[k];
+          float d = g[k];
+          if (CORR) {
+            if (a.corr & LINROUND_DELTA) d -= cv[k];
+            else if (a.corr & LINROUND_CTRL) d += cv[k];
+            if (a.corr & LINROUND_PROX) d = fmaf(a.prox_mu, p - sv[k], d);
+          }
+          d = fmaf(a.wd, p, d);
+          if (a.use_mom) {
+            const float bu = fmaf(mom, mf[k], omd * d);
+            mf[k] = bu;
+            d = a.nesterov ? fmaf(a.mom, bu, d) : bu;
+          }
+          pf[k] = fmaf(-lr, d, p);
+        }
       }
-    }
+    };
+    if (a.corr) backward(std::true_type());
+    else backward(std::false_type());
     __syncthreads();
   }
 

@@ -749,6 +749,137 @@ void multi_diff_accumulate(torch::Tensor server, torch::Tensor replicas,
                      C, n4, (float)wsum, out.data_ptr<float>());
 }
 
+// packed FedGATE / SCAFFOLD state rows, like multi_diff_acc_kernel: one thread
+// per float4 of the arena, the loop over the clients inside the thread in
+// client order (no atomics: bit-reproducible).  Rows with inv[c] == 0 are
+// neither read nor written.  The per-row formulas are delta_kernel's and
+// ctrl_kernel's + wdr_kernel's, expression for expression.
+__global__ void multi_delta_kernel(float* __restrict__ delta,
+                                   const float* __restrict__ server,
+                                   const float* __restrict__ agg,
+                                   const float* __restrict__ replicas,
+                                   const float* __restrict__ inv, long C,
+                                   long n4) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
+       i += stride) {
+    float4 sv = reinterpret_cast<const float4*>(server)[i];
+    float4 av = reinterpret_cast<const float4*>(agg)[i];
+    const float* ss = reinterpret_cast<const float*>(&sv);
+    const float* aa = reinterpret_cast<const float*>(&av);
+    for (long c = 0; c < C; ++c) {
+      const float coef = inv[c];
+      if (coef == 0.f) continue;
+      float4 dv = reinterpret_cast<float4*>(delta + c * n4 * 4)[i];
+      float4 cv = reinterpret_cast<const float4*>(replicas + c * n4 * 4)[i];
+      float* d = reinterpret_cast<float*>(&dv);
+      const float* cc2 = reinterpret_cast<const float*>(&cv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        d[j] = fmaf(coef, ss[j] - aa[j] - cc2[j], d[j]);
+      reinterpret_cast<float4*>(delta + c * n4 * 4)[i] = dv;
+    }
+  }
+}
+
+static void multi_row_check(const char* who, const char* name,
+                            const torch::Tensor& t, at::IntArrayRef shape,
+                            const torch::Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() &&
+                  t.scalar_type() == torch::kFloat && t.is_contiguous() &&
+                  t.sizes() == shape,
+              who, ": ", name, " must be contiguous fp32 ", shape,
+              " on the GPU of the rows, got ", t.sizes());
+}
+
+void multi_delta_update(torch::Tensor delta, torch::Tensor server,
+                        torch::Tensor agg, torch::Tensor replicas,
+                        torch::Tensor inv) {
+  const char* who = "multi_delta_update";
+  TORCH_CHECK(delta.dim() == 2 && delta.is_cuda(), who,
+              ": delta must be [C, N] on GPU");
+  const long C = delta.size(0), N = delta.size(1);
+  TORCH_CHECK(N % 4 == 0, who, ": arena numel must be float4-aligned");
+  multi_row_check(who, "delta", delta, {C, N}, delta);
+  multi_row_check(who, "server", server, {N}, delta);
+  multi_row_check(who, "agg", agg, {N}, delta);
+  multi_row_check(who, "replicas", replicas, {C, N}, delta);
+  multi_row_check(who, "inv", inv, {C}, delta);
+  if (C == 0 || N == 0) return;
+  const long n4 = N / 4;
+  hipLaunchKernelGGL(multi_delta_kernel, dim3(ft_grid(n4)), dim3(FT_BLOCK), 0,
+                     STREAM, delta.data_ptr<float>(),
+                     server.data_ptr<float>(), agg.data_ptr<float>(),
+                     replicas.data_ptr<float>(), inv.data_ptr<float>(), C,
+                     n4);
+}
+
+__global__ void multi_ctrl_kernel(float* __restrict__ ctrl,
+                                  const float* __restrict__ ctrl_server,
+                                  const float* __restrict__ server,
+                                  const float* __restrict__ replicas,
+                                  const float* __restrict__ inv,
+                                  const float* __restrict__ w, long C,
+                                  long n4, float* __restrict__ out) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
+       i += stride) {
+    float4 b = reinterpret_cast<const float4*>(ctrl_server)[i];
+    float4 sv = reinterpret_cast<const float4*>(server)[i];
+    const float* bb = reinterpret_cast<const float*>(&b);
+    const float* ss = reinterpret_cast<const float*>(&sv);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (long c = 0; c < C; ++c) {
+      const float coef = inv[c];
+      if (coef == 0.f) continue;
+      const float wc = w[c];
+      float4 a = reinterpret_cast<float4*>(ctrl + c * n4 * 4)[i];
+      float4 cv = reinterpret_cast<const float4*>(replicas + c * n4 * 4)[i];
+      float4 ov;
+      float* o = reinterpret_cast<float*>(&ov);
+      const float* aa = reinterpret_cast<const float*>(&a);
+      const float* cc3 = reinterpret_cast<const float*>(&cv);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        o[j] = aa[j] - bb[j] + coef * (ss[j] - cc3[j]);
+        acc[j] = fmaf(o[j] - aa[j], wc, acc[j]);
+      }
+      reinterpret_cast<float4*>(ctrl + c * n4 * 4)[i] = ov;
+    }
+    float4 rv;
+    float* rr = reinterpret_cast<float*>(&rv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rr[j] = acc[j];
+    reinterpret_cast<float4*>(out)[i] = rv;
+  }
+}
+
+void multi_scaffold_control_update(torch::Tensor ctrl,
+                                   torch::Tensor ctrl_server,
+                                   torch::Tensor server,
+                                   torch::Tensor replicas, torch::Tensor inv,
+                                   torch::Tensor weights, torch::Tensor out) {
+  const char* who = "multi_scaffold_control_update";
+  TORCH_CHECK(ctrl.dim() == 2 && ctrl.is_cuda(), who,
+              ": ctrl must be [C, N] on GPU");
+  const long C = ctrl.size(0), N = ctrl.size(1);
+  TORCH_CHECK(N % 4 == 0, who, ": arena numel must be float4-aligned");
+  multi_row_check(who, "ctrl", ctrl, {C, N}, ctrl);
+  multi_row_check(who, "ctrl_server", ctrl_server, {N}, ctrl);
+  multi_row_check(who, "server", server, {N}, ctrl);
+  multi_row_check(who, "replicas", replicas, {C, N}, ctrl);
+  multi_row_check(who, "inv", inv, {C}, ctrl);
+  multi_row_check(who, "weights", weights, {C}, ctrl);
+  multi_row_check(who, "out", out, {N}, ctrl);
+  if (N == 0) return;
+  const long n4 = N / 4;
+  hipLaunchKernelGGL(multi_ctrl_kernel, dim3(ft_grid(n4)), dim3(FT_BLOCK), 0,
+                     STREAM, ctrl.data_ptr<float>(),
+                     ctrl_server.data_ptr<float>(), server.data_ptr<float>(),
+                     replicas.data_ptr<float>(), inv.data_ptr<float>(),
+                     weights.data_ptr<float>(), C, n4, out.data_ptr<float>());
+}
+
 // fused decompress + K-way sum: out = sum_k scatter(vs[k] @ idxs[k]) -------
 __global__ void scatter_acc_kernel(const float* __restrict__ vs,
                                    const int* __restrict__ idxs, long total,
@@ -2377,7 +2508,9 @@ torch::Tensor linear_local_rounds(
     torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,
     torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,
     long k_cut, long w_off, long b_off, long K, long loss_kind,
-    double weight_decay, double momentum, double dampening, bool nesterov) {
+    double weight_decay, double momentum, double dampening, bool nesterov,
+    torch::Tensor delta, torch::Tensor ctrl_server, torch::Tensor ctrl_client,
+    double prox_mu) {
   const char* who = "linear_local_rounds";
   TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous(), who,
               ": X must be contiguous [M, F] on GPU");
@@ -2413,6 +2546,23 @@ torch::Tensor linear_local_rounds(
     linround_check(who, "in_mom", in_mom, torch::kFloat, {C, N}, dev);
   const bool has_snap = snap.numel() != 0;
   if (has_snap) linround_check(who, "snap", snap, torch::kFloat, {C, N}, dev);
+  // the gradient correction of the round (an empty tensor: none)
+  const bool has_delta = delta.numel() != 0;
+  const bool has_cs = ctrl_server.numel() != 0;
+  const bool has_cc = ctrl_client.numel() != 0;
+  TORCH_CHECK(has_cs == has_cc, who, ": ctrl_server and ctrl_client come as "
+              "a pair, got only ", has_cs ? "ctrl_server" : "ctrl_client");
+  TORCH_CHECK(!(has_delta && has_cs), who, ": delta and a control pair "
+              "together are not supported (one correction vector per "
+              "client)");
+  if (has_delta)
+    linround_check(who, "delta", delta, torch::kFloat, {C, N}, dev);
+  if (has_cs) {
+    linround_check(who, "ctrl_server", ctrl_server, torch::kFloat, {N}, dev);
+    linround_check(who, "ctrl_client", ctrl_client, torch::kFloat, {C, N},
+                   dev);
+  }
+  TORCH_CHECK(std::isfinite(prox_mu), who, ": prox_mu is not finite");
   TORCH_CHECK(w_off >= 0 && b_off >= 0 && w_off + K * F <= N &&
                   b_off + K <= N &&
                   (w_off + K * F <= b_off || b_off + K <= w_off),
@@ -2454,6 +2604,13 @@ torch::Tensor linear_local_rounds(
   a.use_mom = use_mom; a.nesterov = nesterov;
   a.wd = (float)weight_decay; a.mom = (float)momentum;
   a.omd = (float)(1.0 - dampening);
+  a.corr_rows = has_delta ? delta.data_ptr<float>()
+                : has_cs  ? ctrl_client.data_ptr<float>()
+                          : nullptr;
+  a.ctrl_s = has_cs ? ctrl_server.data_ptr<float>() : nullptr;
+  a.prox_mu = (float)prox_mu;
+  a.corr = (has_delta ? LINROUND_DELTA : 0) | (has_cs ? LINROUND_CTRL : 0) |
+           (prox_mu != 0.0 ? LINROUND_PROX : 0);
 #define LINROUND_LAUNCH(KK, LOSS)                                            \
   hipLaunchKernelGGL((linear_round_k<KK, LOSS>), dim3((unsigned)C),          \
                      dim3(LINROUND_THREADS), 0, STREAM, a)
@@ -2501,6 +2658,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk_compress", &topk_compress);
   m.def("scatter_accumulate", &scatter_accumulate);
   m.def("multi_diff_accumulate", &multi_diff_accumulate);
+  m.def("multi_delta_update", &multi_delta_update);
+  m.def("multi_scaffold_control_update", &multi_scaffold_control_update);
   m.def("fedadam_normalize", &fedadam_normalize);
   m.def("gather_grads", &gather_grads);
   m.def("stem_conv_fwd", &stem_conv_fwd);

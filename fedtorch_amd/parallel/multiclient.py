@@ -28,6 +28,14 @@ from fedtorch_amd import ops
 # models (ops.linear_local_rounds, trainings/packed.py).  Opt-in:
 # ``FEDTORCH_PACKED_BATCHED=1``; timings in profiles/packed_linear_notes.md.
 _BATCHED_ENABLED = os.environ.get('FEDTORCH_PACKED_BATCHED', '0') == '1'
+# The same launch for fedprox / scaffold / dense fedgate (the kernel's
+# gradient-correction term).  A second opt-in on top of the first:
+# ``FEDTORCH_PACKED_BATCHED_CORR=1``.
+_BATCHED_CORR_ENABLED = \
+    os.environ.get('FEDTORCH_PACKED_BATCHED_CORR', '0') == '1'
+
+# federated types the packed trainer implements
+PACKED_TYPES = ('fedavg', 'fedprox', 'scaffold', 'fedgate')
 
 
 class VirtualGraph(object):
@@ -71,6 +79,14 @@ class ClientPack(object):
         self.in_mom = torch.zeros((self.C, n), device=dev) \
             if client.optimizer.param_groups[0]['in_momentum'] else None
         self.mom_init = [False] * self.C
+        # per-algorithm rows: FedGATE's gradient-tracking delta_j, SCAFFOLD's
+        # client controls c_j (the server control is
+        # client.model_server_control)
+        t = getattr(client.args, 'federated_type', None)
+        self.delta = torch.zeros((self.C, n), device=dev) \
+            if t == 'fedgate' else None
+        self.ctrl = torch.zeros((self.C, n), device=dev) \
+            if t == 'scaffold' else None
         self.train_loaders = [None] * self.C
         self.partial = torch.zeros(n, device=dev)
         self._stacked = None  # (X, Y, row offsets), see stacked_data()
@@ -156,7 +172,12 @@ class ClientPack(object):
         if getattr(client.arena, 'half_flat', None) is not None \
                 or getattr(args, 'bf16', False):
             why.append('bf16 compute')
-        if getattr(args, 'federated_type', None) != 'fedavg':
+        t = getattr(args, 'federated_type', None)
+        corr_ok = _BATCHED_CORR_ENABLED \
+            and t in ('fedprox', 'scaffold', 'fedgate') \
+            and not (getattr(args, 'quantized', False)
+                     or getattr(args, 'compressed', False))
+        if t != 'fedavg' and not corr_ok:
             why.append('federated_type is not fedavg')
         opt = client.optimizer
         if getattr(opt, '_prox_mu', 0.0) != 0.0 or any(
@@ -231,13 +252,31 @@ class ClientPack(object):
         if self.in_mom is not None:
             client.optimizer.bind_state(in_buf=self.in_mom[j],
                                         in_init=self.mom_init[j])
-        steps = local_step_fn(self.train_loaders[j])
+        self.arm_correction(j, server_flat)
+        try:
+            steps = local_step_fn(self.train_loaders[j])
+        finally:
+            client.optimizer.clear_correction()
         if self.in_mom is not None:
             self.mom_init[j] = True
         self.replicas[j].copy_(client.arena.flat)
         if self.bufs is not None:
             self.bufs[j].copy_(client.arena.buf_flat)
         return steps
+
+    def arm_correction(self, j, server_flat):
+        """Bind client j's per-step gradient correction on the shared
+        optimizer (the slot loop; `run_client` clears it afterwards)."""
+        t = getattr(self.args, 'federated_type', None)
+        opt = self.base.optimizer
+        if t == 'fedgate':
+            opt.set_correction(delta=self.delta[j])
+        elif t == 'scaffold':
+            opt.set_correction(ctrl_server=self.base.model_server_control,
+                               ctrl_client=self.ctrl[j])
+        elif t == 'fedprox':
+            opt.set_correction(prox_mu=self.args.fedprox_mu,
+                               server=server_flat)
 
     def partial_buffers(self, online_local, total_online):
         """Write this rank's PRE-SCALED partial of the global BN-stat mean
@@ -273,3 +312,29 @@ class ClientPack(object):
         ops.multi_diff_accumulate(server_flat, self.replicas, w,
                                   self.partial)
         return self.partial
+
+    def _inv_lr_tau(self, weights, taus, lrs, device):
+        """[C] fp32: 1 / (lr_j tau_j) of the clients that took part
+        (w_j != 0 and tau_j > 0), 0 for the others."""
+        return torch.tensor(
+            [1.0 / (lr * tau) if w != 0.0 and tau > 0 else 0.0
+             for w, tau, lr in zip(weights, taus, lrs)],
+            dtype=torch.float32, device=device)
+
+    def update_delta(self, server_flat, agg, weights, taus, lrs):
+        """FedGATE: delta_j += (server - agg - y_j) / (lr_j tau_j) for the
+        clients that took part; `agg` is the all-reduced partial and
+        `server_flat` the server BEFORE the aggregate is applied."""
+        ops.multi_delta_update(
+            self.delta, server_flat, agg, self.replicas,
+            self._inv_lr_tau(weights, taus, lrs, server_flat.device))
+
+    def update_controls(self, server_flat, weights, taus, lrs, out):
+        """SCAFFOLD: c_j+ = c_j - c + (server - y_j) / (tau_j lr_j) for the
+        clients that took part, out = sum_j w_j (c_j+ - c_j), c_j <- c_j+."""
+        dev = server_flat.device
+        ops.multi_scaffold_control_update(
+            self.ctrl, self.base.model_server_control, server_flat,
+            self.replicas, self._inv_lr_tau(weights, taus, lrs, dev),
+            torch.tensor(weights, dtype=torch.float32, device=dev), out)
+        return out

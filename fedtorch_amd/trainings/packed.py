@@ -4,6 +4,19 @@
 on 8 ranks).  Aggregation math is identical to W*C one-client ranks: each
 rank reduces its local clients' weighted diffs into ONE partial and a
 single world all-reduce finishes the sum.
+
+Algorithms: FedAvg, FedProx, SCAFFOLD and dense FedGATE, each optionally
+DRFA lambda-weighted.  With x the server, y_j client j's replica after its
+tau_j local steps, lr_j the lr of its last step, w_j its weight:
+
+    partial = sum_j w_j (x - y_j) ; all_reduce ; x -= lr_scale_at_sync * partial
+    fedgate   after the all-reduce (d = reduced partial, x before the update):
+              delta_j += (x - d - y_j) / (lr_j tau_j)
+    scaffold  before it: c_j+ = c_j - c + (x - y_j) / (tau_j lr_j),
+              b = sum_j w_j (c_j+ - c_j), c_j <- c_j+ ; [partial | b] travel
+              in one 2N all-reduce ; c += b |S| / N_tot
+for the clients with w_j != 0 and tau_j > 0; the per-step gradient
+corrections are those of `ops.fused_sgd_step`.
 """
 import time
 
@@ -17,7 +30,9 @@ from fedtorch_amd.trainings.flow import (
 from fedtorch_amd.trainings.eval import inference
 from fedtorch_amd.trainings.federated import amp
 from fedtorch_amd.trainings.afl import lambda_dual_update
-from fedtorch_amd.aggregation.federated import distribute_model_server
+from fedtorch_amd.aggregation.federated import (
+    distribute_model_server, distribute_model_server_control)
+from fedtorch_amd.parallel.multiclient import PACKED_TYPES
 from fedtorch_amd.logs.logging import log, logging_load_time
 from fedtorch_amd.logs.meter import define_local_training_tracker
 
@@ -92,7 +107,8 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut):
     step's rows from the loader's index_batches() (a fresh epoch whenever one
     runs out, like the `while` / `for` pair of `_local_steps_fn`).  `snap`:
     DRFA's [C, N] snapshot arena, row j receives client j's parameters before
-    its step `k_cut`."""
+    its step `k_cut`.  Returns (loss [C, T], steps per client, lr of each
+    client's last step)."""
     args = client.args
     _X, _Y, offs = pack.stacked_data()
     plan = [None] * pack.C
@@ -131,24 +147,51 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut):
                             dtype=torch.int32).to(dev)
     w_off, b_off, K, _F = pack.linear_layout()
     from fedtorch_amd.components.models.convex import LeastSquare
+    corr = {}
+    if args.federated_type == 'fedgate':
+        corr['delta'] = pack.delta
+    elif args.federated_type == 'scaffold':
+        corr.update(ctrl_server=client.model_server_control,
+                    ctrl_client=pack.ctrl)
+    elif args.federated_type == 'fedprox':
+        corr['prox_mu'] = args.fedprox_mu
     loss = ops.linear_local_rounds(
         _X, _Y, idx.to(dev), steps.to(dev), lr.to(dev), server,
         pack.replicas, pack.in_mom if momentum != 0 else None, mom_init,
         snap, k_cut, w_off=w_off, b_off=b_off, K=K,
         loss_kind=1 if isinstance(client.model, LeastSquare) else 0,
         weight_decay=g['weight_decay'], momentum=momentum,
-        dampening=g['dampening'], nesterov=g['nesterov'])
+        dampening=g['dampening'], nesterov=g['nesterov'], **corr)
     if pack.in_mom is not None:
         for j, p in enumerate(plan):
             if p:
                 pack.mom_init[j] = True
-    return loss
+    return (loss, [len(p) if p else 0 for p in plan],
+            [p[-1][1] if p else 0.0 for p in plan])
+
+
+def check_packed_supported(args):
+    """Raise for what the packed trainer does not implement (it would
+    otherwise train plain FedAvg under another algorithm's name)."""
+    t = args.federated_type
+    if t not in PACKED_TYPES:
+        raise ValueError(
+            '--federated_type {} is not implemented with --clients_per_rank '
+            '> 1; the packed trainer runs {}'.format(
+                t, ', '.join(PACKED_TYPES)))
+    if t == 'fedgate' and (args.quantized or args.compressed):
+        raise ValueError(
+            'FedCOMGATE (--federated_type fedgate with --quantized / '
+            '--compressed) is not implemented with --clients_per_rank > 1; '
+            'pass --quantized false --compressed false for dense FedGATE')
 
 
 def train_and_validate_federated_packed(client, pack, validate=False):
-    """FedAvg (optionally DRFA lambda-weighted) over packed virtual
-    clients."""
+    """FedAvg / FedProx / SCAFFOLD / dense FedGATE (optionally DRFA
+    lambda-weighted) over packed virtual clients."""
     args = client.args
+    check_packed_supported(args)
+    ftype = args.federated_type
     drfa = args.federated_drfa
     total = pack.total_clients
     log('packed federated training: {} ranks x {} virtual clients'.format(
@@ -171,11 +214,18 @@ def train_and_validate_federated_packed(client, pack, validate=False):
         args.debug)
     run_client = (lambda j, server_flat, fn: None) if batched \
         else pack.run_client
+    if ftype == 'scaffold':
+        ctrl_server = client.model_server_control
+        pair = torch.zeros(2 * server.numel(), device=server.device)
     for n_c in range(args.num_comms):
         args.rounds_comm += 1
         args.comm_time.append(0.0)
         online = client.comm.sample_online_global(total)
-        distribute_model_server(client.comm, server)
+        if ftype == 'scaffold':
+            distribute_model_server_control(client.comm, server, ctrl_server,
+                                            client.work)
+        else:
+            distribute_model_server(client.comm, server)
         if drfa:
             client.comm.broadcast(lambda_vector, src=0)
             k_cut = torch.randint(low=1, high=max(args.local_step, 2),
@@ -189,6 +239,7 @@ def train_and_validate_federated_packed(client, pack, validate=False):
         n_online = len(online) if 0 in online else len(online) + 1
         n_online = max(n_online, 1)
         weights = []
+        taus, lrs = [0] * pack.C, [0.0] * pack.C
         for j in range(pack.C):
             gid = pack.global_id(j)
             if gid in online:
@@ -228,20 +279,35 @@ def train_and_validate_federated_packed(client, pack, validate=False):
                                 if is_sync:
                                     break
                         return steps
-                    run_client(j, server, step_and_snapshot)
+                    taus[j] = run_client(j, server, step_and_snapshot)
                 else:
                     w = 1.0 / n_online
-                    run_client(j, server, step_fn)
+                    taus[j] = run_client(j, server, step_fn)
+                lrs[j] = client.optimizer.param_groups[0]['lr']
             else:
                 w = 0.0
             weights.append(w)
         if batched:
-            _batched_local_rounds(client, pack, server, online,
-                                  kth if drfa else None,
-                                  k_cut if drfa else 0)
+            _loss, taus, lrs = _batched_local_rounds(
+                client, pack, server, online, kth if drfa else None,
+                k_cut if drfa else 0)
 
         partial = pack.accumulate_partial(server, weights)
-        client.comm.all_reduce(partial)
+        if ftype == 'scaffold':
+            # [partial | weighted control delta] in one 2N all-reduce
+            n = server.numel()
+            pack.update_controls(server, weights, taus, lrs, pair[n:])
+            pair[:n].copy_(partial)
+            client.comm.all_reduce(pair)
+            partial.copy_(pair[:n])
+            # c += sum_j w_j (c_j+ - c_j) |S| / N: sign and factor as in
+            # aggregation.federated.scaffold_aggregation
+            ctrl_server.add_(pair[n:], alpha=len(online) / total)
+        else:
+            client.comm.all_reduce(partial)
+        if ftype == 'fedgate':
+            # before the server moves: delta_j uses the round's own server
+            pack.update_delta(server, partial, weights, taus, lrs)
         _apply_aggregate(client, server, partial)
         client.arena.load_flat(server)
         # BN running stats: each rank contributes its pre-scaled partial

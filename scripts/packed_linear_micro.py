@@ -6,7 +6,11 @@ linear_local_rounds launch for all clients, hip/linearround.h).  Needs a GPU.
 
 Configurations: synthetic logistic regression (60 -> 10) and MNIST logistic
 regression (784 -> 10), B = 50, tau = 10, C in {16, 128} virtual clients on
-one rank, every client online, momentum 0.9 on and off.
+one rank, every client online, momentum 0.9 on and off (--momentum).
+--federated_type fedprox / scaffold / fedgate times the same two paths for
+the algorithms that need the kernel's gradient-correction term; the batched
+path then also needs FEDTORCH_PACKED_BATCHED_CORR, which this script sets
+together with the first flag.
 
 Per configuration ONE process builds the federation once, warms both paths
 up, then runs --rounds rounds of each path ALTERNATELY; a round is timed
@@ -31,14 +35,14 @@ from fedtorch_amd.parallel import multiclient  # noqa: E402
 B, TAU = 50, 10
 
 
-def federation(data, C, momentum):
+def federation(data, C, momentum, ftype='fedavg'):
     from fedtorch_amd.parameters import get_args
     from fedtorch_amd.nodes import Client
     os.environ['FEDTORCH_SYNTH_SIZE'] = str(C * 500)
     torch.manual_seed(1)
     np.random.seed(1)
     argv = ['-d', data, '-a', 'logistic_regression', '-f', 'true',
-            '--federated_type', 'fedavg', '--num_comms', '1',
+            '--federated_type', ftype, '--num_comms', '1',
             '--clients_per_rank', str(C), '-b', str(B), '--lr', '0.05',
             '--federated_sync_type', 'local_step', '--local_step', str(TAU),
             '--online_client_rate', '1.0',
@@ -74,6 +78,7 @@ def one_round(client, pack, batched):
     from fedtorch_amd.trainings.packed import \
         train_and_validate_federated_packed
     multiclient._BATCHED_ENABLED = batched
+    multiclient._BATCHED_CORR_ENABLED = batched
     assert pack.batched_eligible() == batched, pack.batched_blockers()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -88,18 +93,22 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--clients', type=str, default='16,128')
     ap.add_argument('--data', type=str, default='synthetic,mnist')
+    ap.add_argument('--momentum', type=str, default='on,off')
+    ap.add_argument('--federated_type', type=str, default='fedavg')
     a = ap.parse_args()
     if not (torch.cuda.is_available() and ops.hip_available()):
         raise SystemExit('packed_linear_micro needs a GPU and the built '
                          'kernel pack')
-    old = multiclient._BATCHED_ENABLED
+    old = multiclient._BATCHED_ENABLED, multiclient._BATCHED_CORR_ENABLED
     try:
         for data in a.data.split(','):
             for C in [int(c) for c in a.clients.split(',')]:
-                for momentum in (True, False):
-                    tag = '%s C=%d momentum=%s' % (data, C,
-                                                   'on' if momentum else 'off')
-                    client, pack = federation(data, C, momentum)
+                for momentum in [m == 'on' for m in a.momentum.split(',')]:
+                    tag = '%s %s C=%d momentum=%s' % (
+                        a.federated_type, data, C,
+                        'on' if momentum else 'off')
+                    client, pack = federation(data, C, momentum,
+                                              a.federated_type)
                     for _ in range(a.warmup):
                         for batched in (False, True):
                             one_round(client, pack, batched)
@@ -120,7 +129,7 @@ def main():
                               statistics.median(s) / statistics.median(f)),
                           flush=True)
     finally:
-        multiclient._BATCHED_ENABLED = old
+        multiclient._BATCHED_ENABLED, multiclient._BATCHED_CORR_ENABLED = old
     print('PACKED_LINEAR_MICRO_OK')
 
 
