@@ -456,6 +456,214 @@ def linear_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
 
 
 # --------------------------------------------------------------------------
+# packed MLP: all clients' local steps batched per layer (hip/mlpround.h)
+# --------------------------------------------------------------------------
+
+# kept equal to MLPROUND_MAXB / _MAXK / _MAXL of hip/mlpround.h (a GPU test
+# compares)
+MLPROUND_MAXB = 64
+MLPROUND_MAXK = 128
+MLPROUND_MAXL = 8
+
+
+def mlp_round_max_batch():
+    """largest batch size B of ops.mlp_local_rounds (the smallest is 2)"""
+    return MLPROUND_MAXB
+
+
+def mlp_round_max_classes():
+    """largest class count K of ops.mlp_local_rounds"""
+    return MLPROUND_MAXK
+
+
+def _mlp_layout_flat(layout):
+    """[L, (w, b, gamma, beta, in, out) x L, fc, H, K] of a layout dict"""
+    blocks = [tuple(int(v) for v in blk) for blk in layout['blocks']]
+    head = tuple(int(v) for v in layout['head'])
+    if any(len(blk) != 6 for blk in blocks) or len(head) != 3:
+        raise ValueError('mlp_local_rounds: a layout block is (w_off, b_off, '
+                         'gamma_off, beta_off, in, out), the head (fc_off, '
+                         'H, K)')
+    flat = [len(blocks)]
+    for blk in blocks:
+        flat.extend(blk)
+    flat.extend(head)
+    return flat
+
+
+def _mlp_layout_check(layout, F, N):
+    """the launcher's layout checks for the eager twin; returns the spans
+    [(start, end)] of the parameter tensors in the arena"""
+    who = 'mlp_local_rounds: '
+    flat = _mlp_layout_flat(layout)
+    L = flat[0]
+    if not 1 <= L <= MLPROUND_MAXL:
+        raise ValueError(who + 'layout has %d blocks (1 <= L <= %d)'
+                         % (L, MLPROUND_MAXL))
+    spans, prev = [], F
+    for i, (w, b, g, be, fin, out) in enumerate(layout['blocks']):
+        if fin != prev or out < 1:
+            raise ValueError(who + 'layout block %d is [%d, %d] but its '
+                             'input has %d features' % (i, out, fin, prev))
+        spans += [(w, w + fin * out), (b, b + out), (g, g + out),
+                  (be, be + out)]
+        prev = out
+    fc, H, K = layout['head']
+    if H != prev:
+        raise ValueError(who + 'layout head reads %d features but the last '
+                         'block has %d' % (H, prev))
+    if not 1 <= K <= MLPROUND_MAXK:
+        raise ValueError(who + 'unsupported K=%d (1 <= K <= %d)'
+                         % (K, MLPROUND_MAXK))
+    spans.append((fc, fc + H * K))
+    for lo, hi in spans:
+        if lo < 0 or hi > N:
+            raise ValueError(who + 'layout tensor [%d, %d) does not fit the '
+                             'arena of %d' % (lo, hi, N))
+    order = sorted(spans)
+    for (_l0, h0), (l1, _h1) in zip(order, order[1:]):
+        if h0 > l1:
+            raise ValueError(who + 'layout tensors overlap at arena element '
+                             '%d' % l1)
+    return spans
+
+
+def mlp_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
+                     mom_init, snap, k_cut, *, layout, eps, wd_numel,
+                     weight_decay, momentum, dampening, nesterov):
+    """All local SGD steps of a round, for every packed client of an MLP
+    (`components/models/mlp.py` without noise), batched per layer.
+
+    X [M, F] f32, Y [M] int32 class ids; idx [C, T, B] int32 rows of X per
+    sample, -1 = padding, 2 <= B <= 64; steps [C] int32 (0 = offline, nothing
+    of that client is read or written); lr [C, T] f32; server [N];
+    replicas [C, N] (out); in_mom [C, N] or None/empty; mom_init [C] int32
+    (in/out); snap [C, N] or None/empty: parameters BEFORE step k_cut
+    (1-based), written when 1 <= k_cut <= steps[c].
+
+    layout: dict(blocks=[(w_off, b_off, gamma_off, beta_off, in, out), ...],
+    head=(fc_off, H, K)): the arena offsets and shapes of the L blocks
+    Linear(in, out) + BatchNorm1d(out) + ReLU and of the bias-free head
+    Linear(H, K), K <= 128.  BatchNorm uses the batch's statistics (biased
+    variance, `eps`, affine).
+
+    for every client c with steps[c] > 0:
+      replicas[c] <- server                    (whole row, pad gaps included)
+      for s in 0 .. steps[c]-1, rows r = idx[c, s, :] >= 0, n = #rows >= 2:
+        [snap[c] <- replicas[c]   if s + 1 == k_cut]
+        a_0 = X[r]
+        z_i = a_i W_i^T + b_i ; mu, var over the n rows
+        xh = (z - mu) rsqrt(var + eps) ; y_i = g_i xh + beta_i
+        a_{i+1} = max(y_i, 0)
+        logits = a_L Wfc^T ; loss[c, s] = mean CE(logits, Y[r])
+        backward of exactly that ; d = grad (+ wd p for arena index
+        < wd_numel) ; momentum / dampening / nesterov / first use
+        (mom_init[c] == 0 at s == 0: buf = d) ; p -= lr[c, s] d
+        -- the local branch of `fused_sgd_step`, in place in replicas[c]
+        (and in_mom[c])
+      mom_init[c] <- 1 (with momentum)
+
+    Pad gaps of in_mom stay as they were; in_mom / mom_init are touched only
+    when momentum != 0.  Returns loss [C, T]: the mean loss of each executed
+    step, 0 elsewhere.  The eager twin raises ValueError for an executed
+    step with fewer than 2 valid rows; the HIP path cannot see a device idx
+    and stays in bounds and finite there (n = 1 gives xh = 0)."""
+    dev = X.device
+    if in_mom is None:
+        in_mom = torch.empty(0, device=dev)
+    if snap is None:
+        snap = torch.empty(0, device=dev)
+    if _use_hip(X, server, replicas):
+        return _C.mlp_local_rounds(
+            X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap,
+            int(k_cut), _mlp_layout_flat(layout), float(eps), int(wd_numel),
+            float(weight_decay), float(momentum), float(dampening),
+            bool(nesterov))
+
+    # eager twin: a per-client, per-step loop; the gradients come from
+    # autograd over F.linear / F.batch_norm / F.relu / F.cross_entropy, the
+    # update from the fused-SGD twin above over the whole row — the ops of
+    # the packed slot loop, in its order.  Pad gaps (zero in a real arena,
+    # where the whole-row update leaves them zero) are put back afterwards.
+    import torch.nn.functional as Fn
+    C, T, B = idx.shape
+    N = server.numel()
+    spans = _mlp_layout_check(layout, X.shape[1], N)
+    if not 2 <= B <= MLPROUND_MAXB:
+        raise ValueError('mlp_local_rounds: unsupported B=%d (2 <= B <= %d)'
+                         % (B, MLPROUND_MAXB))
+    if k_cut < 0:
+        raise ValueError('mlp_local_rounds: k_cut is %d, expected >= 0'
+                         % k_cut)
+    n_steps = steps.tolist()
+    if max(n_steps) > T:
+        raise ValueError('mlp_local_rounds: steps holds %d but idx has T=%d'
+                         % (max(n_steps), T))
+    for c in range(C):
+        for s in range(n_steps[c]):
+            if int((idx[c, s] >= 0).sum()) < 2:
+                raise ValueError(
+                    'mlp_local_rounds: step %d of client %d has fewer than 2 '
+                    'samples (BatchNorm needs the batch statistics)' % (s, c))
+    use_mom = momentum != 0
+    loss = torch.zeros((C, T), dtype=torch.float32, device=dev)
+    inits = mom_init.tolist()
+    gap = torch.ones_like(server, dtype=torch.bool)
+    for lo, hi in spans:
+        gap[lo:hi] = False
+    shapes = []                              # (offset, shape) in forward order
+    for w, b, g, be, fin, out in layout['blocks']:
+        shapes += [(w, (out, fin)), (b, (out,)), (g, (out,)), (be, (out,))]
+    fc, H, K = layout['head']
+    shapes.append((fc, (K, H)))
+    for c in range(C):
+        if n_steps[c] <= 0:
+            continue
+        p = server.clone()
+        grad = torch.zeros_like(p)
+        mom_gaps = in_mom[c][gap].clone() if use_mom else None
+        for s in range(n_steps[c]):
+            if snap.numel() and s + 1 == k_cut:
+                snap[c].copy_(torch.where(gap, server, p))
+            rows = idx[c, s]
+            rows = rows[rows >= 0].long()
+            ts = []
+            for off, shp in shapes:
+                n_el = 1
+                for v in shp:
+                    n_el *= v
+                ts.append(p[off:off + n_el].view(shp).clone()
+                          .requires_grad_(True))
+            with torch.enable_grad():
+                a = X[rows]
+                for i in range(len(layout['blocks'])):
+                    w_, b_, g_, be_ = ts[4 * i:4 * i + 4]
+                    a = Fn.relu(Fn.batch_norm(Fn.linear(a, w_, b_), None,
+                                              None, g_, be_, True, 0.1, eps))
+                l = Fn.cross_entropy(Fn.linear(a, ts[-1]), Y[rows].long())
+                gs = torch.autograd.grad(l, ts)
+            loss[c, s] = l.detach()
+            grad.zero_()
+            for (off, _shp), gt in zip(shapes, gs):
+                grad[off:off + gt.numel()].copy_(gt.reshape(-1))
+            fused_sgd_step(
+                p, grad, lr=float(lr[c, s]), scale=1.0,
+                weight_decay=weight_decay, in_momentum=momentum,
+                out_momentum=0.0, dampening=dampening, nesterov=nesterov,
+                apply_lr=True, apply_in_momentum=use_mom,
+                apply_out_momentum=False,
+                in_buf=in_mom[c] if use_mom else None,
+                first_in=use_mom and not inits[c], wd_numel=wd_numel)
+            if use_mom:
+                inits[c] = 1
+        replicas[c].copy_(torch.where(gap, server, p))
+        if use_mom:
+            in_mom[c][gap] = mom_gaps
+            mom_init[c] = 1
+    return loss
+
+
+# --------------------------------------------------------------------------
 # small host-side math (not perf-critical)
 # --------------------------------------------------------------------------
 

@@ -21,6 +21,7 @@
 #include "head.h"
 #include "gru.h"
 #include "linearround.h"
+#include "mlpround.h"
 
 #define CHK(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
 #define STREAM at::hip::getCurrentHIPStream().stream()
@@ -2631,7 +2632,184 @@ torch::Tensor linear_local_rounds(
   return loss;
 }
 
+// ==========================================================================
+// packed MLP: all clients' local steps batched per layer (mlpround.h)
+// ==========================================================================
+long mlp_round_max_batch() { return MLPROUND_MAXB; }
+long mlp_round_max_classes() { return MLPROUND_MAXK; }
+long mlp_round_max_layers() { return MLPROUND_MAXL; }
+
+// layout: [L, (w, b, gamma, beta, in, out) x L, fc, H, K] -- arena offsets
+// and shapes of the blocks and of the head.  Returns loss [C, T]; writes
+// replicas / in_mom / mom_init / snap rows of the clients with steps > 0.
+// idx and steps are range-checked on the host unless the stream is
+// capturing (the kernels never read X outside [0, M)).
+torch::Tensor mlp_local_rounds(
+    torch::Tensor X, torch::Tensor Y, torch::Tensor idx, torch::Tensor steps,
+    torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,
+    torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,
+    long k_cut, std::vector<int64_t> layout, double eps, long wd_numel,
+    double weight_decay, double momentum, double dampening, bool nesterov) {
+  const char* who = "mlp_local_rounds";
+  TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous(), who,
+              ": X must be contiguous [M, F] on GPU");
+  TORCH_CHECK(X.scalar_type() == torch::kFloat, who, ": X must be fp32");
+  const long M = X.size(0), F = X.size(1);
+  const auto dev = X.device();
+  TORCH_CHECK(M >= 1 && F >= 1, who, ": empty X");
+  TORCH_CHECK(M < (1L << 31) && F < (1L << 21), who, ": X too large");
+  TORCH_CHECK(server.dim() == 1 && server.size(0) < (1L << 30), who,
+              ": server must be [N], N < 2^30");
+  const long N = server.size(0);
+  linround_check(who, "Y", Y, torch::kInt, {M}, dev);
+  TORCH_CHECK(idx.dim() == 3, who, ": idx must be [C, T, B], got ",
+              idx.sizes());
+  const long C = idx.size(0), T = idx.size(1), B = idx.size(2);
+  TORCH_CHECK(C >= 1 && T >= 1, who, ": empty idx");
+  TORCH_CHECK(C < 65536 && T < (1L << 31), who, ": idx too large");
+  TORCH_CHECK(B >= 2 && B <= MLPROUND_MAXB, who, ": unsupported B=", B,
+              " (2 <= B <= ", MLPROUND_MAXB, ")");
+  linround_check(who, "idx", idx, torch::kInt, {C, T, B}, dev);
+  linround_check(who, "steps", steps, torch::kInt, {C}, dev);
+  linround_check(who, "lr", lr, torch::kFloat, {C, T}, dev);
+  linround_check(who, "server", server, torch::kFloat, {N}, dev);
+  linround_check(who, "replicas", replicas, torch::kFloat, {C, N}, dev);
+  linround_check(who, "mom_init", mom_init, torch::kInt, {C}, dev);
+  const bool use_mom = momentum != 0.0;
+  if (use_mom)
+    linround_check(who, "in_mom", in_mom, torch::kFloat, {C, N}, dev);
+  const bool has_snap = snap.numel() != 0;
+  if (has_snap) linround_check(who, "snap", snap, torch::kFloat, {C, N}, dev);
+  TORCH_CHECK(k_cut >= 0, who, ": k_cut is ", k_cut, ", expected >= 0");
+  TORCH_CHECK(!nesterov || (use_mom && dampening == 0.0), who,
+              ": nesterov needs a momentum and zero dampening");
+  TORCH_CHECK(std::isfinite(eps) && eps > 0.0, who, ": eps must be > 0");
+  TORCH_CHECK(wd_numel >= 0 && wd_numel <= N, who, ": wd_numel is ", wd_numel,
+              ", the arena has ", N);
+
+  // the layout
+  TORCH_CHECK(!layout.empty(), who, ": empty layout");
+  const long L = layout[0];
+  TORCH_CHECK(L >= 1 && L <= MLPROUND_MAXL, who, ": layout has ", L,
+              " blocks (1 <= L <= ", MLPROUND_MAXL, ")");
+  TORCH_CHECK((long)layout.size() == 1 + 6 * L + 3, who, ": layout of ", L,
+              " blocks must hold ", 1 + 6 * L + 3, " numbers, got ",
+              layout.size());
+  MlpLayout lay;
+  lay.L = (int)L;
+  std::vector<std::pair<long, long>> spans;      // [start, end) in the arena
+  auto span = [&](long off, long len, const char* what, long i) {
+    TORCH_CHECK(off >= 0 && len >= 1 && off + len <= N, who, ": layout ",
+                what, " of block ", i, " [", off, ", +", len,
+                ") does not fit the arena of ", N);
+    spans.emplace_back(off, off + len);
+  };
+  long prev = F;
+  for (long i = 0; i < L; ++i) {
+    const int64_t* e = layout.data() + 1 + 6 * i;
+    const long in = e[4], out = e[5];
+    // column tiles are the grid's y dimension (<= 65535 blocks of 32)
+    TORCH_CHECK(in == prev && out >= 1 && out < (1L << 21), who,
+                ": layout block ", i, " is [", out, ", ", in,
+                "] but its input has ", prev, " features");
+    span(e[0], in * out, "weight", i);
+    span(e[1], out, "bias", i);
+    span(e[2], out, "gamma", i);
+    span(e[3], out, "beta", i);
+    lay.w[i] = (int)e[0]; lay.b[i] = (int)e[1]; lay.g[i] = (int)e[2];
+    lay.be[i] = (int)e[3]; lay.in[i] = (int)in; lay.out[i] = (int)out;
+    prev = out;
+  }
+  const int64_t* h = layout.data() + 1 + 6 * L;
+  const long H = h[1], K = h[2];
+  TORCH_CHECK(H == prev, who, ": layout head reads ", H,
+              " features but the last block has ", prev);
+  TORCH_CHECK(K >= 1 && K <= MLPROUND_MAXK, who, ": unsupported K=", K,
+              " (1 <= K <= ", MLPROUND_MAXK, ")");
+  span(h[0], H * K, "head weight", L);
+  lay.fc = (int)h[0]; lay.H = (int)H; lay.K = (int)K;
+  std::sort(spans.begin(), spans.end());
+  for (size_t i = 1; i < spans.size(); ++i)
+    TORCH_CHECK(spans[i - 1].second <= spans[i].first, who,
+                ": layout tensors overlap at arena element ", spans[i].first);
+
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(STREAM, &cap) == hipSuccess, who,
+              ": hipStreamIsCapturing failed");
+  if (cap == hipStreamCaptureStatusNone) {
+    const long top = idx.max().item<int>();
+    TORCH_CHECK(top < M, who, ": idx holds row ", top, " but X has ", M,
+                " rows");
+    const long most = steps.max().item<int>();
+    TORCH_CHECK(most <= T, who, ": steps holds ", most, " but idx has T=", T);
+  }
+
+  // workspace per client: xh, a, rstd per block; dz per block; dlogits
+  long off = 0;
+  for (long i = 0; i < L; ++i) {
+    lay.xh[i] = (int)off;   off += B * lay.out[i];
+    lay.act[i] = (int)off;  off += B * lay.out[i];
+    lay.rstd[i] = (int)off; off += lay.out[i];
+    lay.dz[i] = (int)off;   off += B * lay.out[i];
+  }
+  lay.dz[L] = (int)off; off += B * K;
+  TORCH_CHECK(off < (1L << 31), who, ": workspace too large");
+  lay.ws_stride = off;
+  auto ws = torch::empty({C, off}, X.options());
+  auto loss = torch::zeros({C, T}, X.options());
+
+  MlpRoundArgs a;
+  a.X = X.data_ptr<float>();
+  a.Y = Y.data_ptr<int>();
+  a.idx = idx.data_ptr<int>();
+  a.steps = steps.data_ptr<int>();
+  a.lr = lr.data_ptr<float>();
+  a.server = server.data_ptr<float>();
+  a.replicas = replicas.data_ptr<float>();
+  a.in_mom = use_mom ? in_mom.data_ptr<float>() : nullptr;
+  a.mom_init = mom_init.data_ptr<int>();
+  a.snap = has_snap ? snap.data_ptr<float>() : nullptr;
+  a.loss = loss.data_ptr<float>();
+  a.ws = ws.data_ptr<float>();
+  a.M = (int)M; a.B = (int)B; a.T = (int)T; a.N = (int)N;
+  a.k_cut = (int)std::min<long>(k_cut, 1L << 30);
+  a.use_mom = use_mom; a.nesterov = nesterov; a.wd_numel = (int)wd_numel;
+  a.wd = (float)weight_decay; a.mom = (float)momentum;
+  a.omd = (float)(1.0 - dampening); a.eps = (float)eps;
+  a.lay = lay;
+
+  const dim3 blk(MLPROUND_THREADS);
+  auto tiles = [](long n) { return (unsigned)((n + MLP_TN - 1) / MLP_TN); };
+  const unsigned rowb =
+      (unsigned)std::min<long>((N + 4 * MLPROUND_THREADS - 1) /
+                                   (4 * MLPROUND_THREADS), 64);
+  const unsigned Cu = (unsigned)C;
+  hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, rowb), blk, 0, STREAM, a, 0);
+  for (int s = 0; s < (int)T; ++s) {
+    if (has_snap && s + 1 == k_cut)
+      hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, rowb), blk, 0, STREAM, a, 1);
+    hipLaunchKernelGGL(mlp_fwd_layer_k<true>, dim3(Cu, tiles(lay.out[0])),
+                       blk, 0, STREAM, a, s, 0);
+    for (int i = 1; i < (int)L; ++i)
+      hipLaunchKernelGGL(mlp_fwd_layer_k<false>, dim3(Cu, tiles(lay.out[i])),
+                         blk, 0, STREAM, a, s, i);
+    hipLaunchKernelGGL(mlp_head_k, dim3(Cu), blk, 0, STREAM, a, s);
+    for (int i = (int)L - 1; i >= 0; --i)
+      hipLaunchKernelGGL(mlp_bwd_k<false>, dim3(Cu, tiles(lay.out[i])), blk,
+                         0, STREAM, a, s, i);
+    hipLaunchKernelGGL(mlp_bwd_k<true>, dim3(Cu, tiles(lay.in[0])), blk, 0,
+                       STREAM, a, s, 0);
+  }
+  if (use_mom)
+    hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, 1), blk, 0, STREAM, a, 2);
+  return loss;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("mlp_local_rounds", &mlp_local_rounds);
+  m.def("mlp_round_max_batch", &mlp_round_max_batch);
+  m.def("mlp_round_max_classes", &mlp_round_max_classes);
+  m.def("mlp_round_max_layers", &mlp_round_max_layers);
   m.def("linear_local_rounds", &linear_local_rounds);
   m.def("linear_round_max_floats", &linear_round_max_floats);
   m.def("linear_round_lds_floats", &linear_round_lds_floats);

@@ -34,6 +34,12 @@ _BATCHED_ENABLED = os.environ.get('FEDTORCH_PACKED_BATCHED', '0') == '1'
 _BATCHED_CORR_ENABLED = \
     os.environ.get('FEDTORCH_PACKED_BATCHED_CORR', '0') == '1'
 
+# Packed MLP clients: the local steps of all online clients batched per layer
+# (ops.mlp_local_rounds, hip/mlpround.h).  Its own opt-in:
+# ``FEDTORCH_PACKED_BATCHED_MLP=1``; timings in profiles/packed_mlp_notes.md.
+_BATCHED_MLP_ENABLED = \
+    os.environ.get('FEDTORCH_PACKED_BATCHED_MLP', '0') == '1'
+
 # federated types the packed trainer implements
 PACKED_TYPES = ('fedavg', 'fedprox', 'scaffold', 'fedgate')
 
@@ -224,6 +230,113 @@ class ClientPack(object):
 
     def batched_eligible(self):
         return not self.batched_blockers()
+
+    # ---- batched round of an MLP (trainings/packed.py) ---------------------
+    def mlp_layout(self):
+        """The layout ops.mlp_local_rounds takes -- dict(blocks=[(w_off,
+        b_off, gamma_off, beta_off, in, out), ...], head=(fc_off, H, K)) --
+        of the compute module in the arena, or None when the module is not a
+        plain MLP (no noise, BatchNorm on batch statistics, Dropout p = 0)
+        whose parameters are exactly the arena's."""
+        import torch.nn as nn
+        from fedtorch_amd.components.models.mlp import MLP
+        model, arena = self.base.model, self.base.arena
+        if type(model) is not MLP or model.noise is not None:
+            return None
+        names = ['fc.weight']
+        for i, blk in enumerate(model.layers):
+            if len(blk) != 4 or not isinstance(blk[0], nn.Linear) \
+                    or not isinstance(blk[1], nn.BatchNorm1d) \
+                    or not isinstance(blk[2], nn.ReLU) \
+                    or not isinstance(blk[3], nn.Dropout):
+                return None
+            if blk[1].track_running_stats or not blk[1].affine \
+                    or blk[0].bias is None or blk[3].p != 0:
+                return None
+            names += ['layers.%d.%d.%s' % (i, k, w) for k in (0, 1)
+                      for w in ('weight', 'bias')]
+        if model.fc.bias is not None or len(model.layers) < 1 \
+                or sorted(arena.names) != sorted(names):
+            return None
+        off = lambda n: arena.offsets[arena.names.index(n)]  # noqa: E731
+        blocks = []
+        for i, blk in enumerate(model.layers):
+            out, fin = blk[0].weight.shape
+            blocks.append((off('layers.%d.0.weight' % i),
+                           off('layers.%d.0.bias' % i),
+                           off('layers.%d.1.weight' % i),
+                           off('layers.%d.1.bias' % i), int(fin), int(out)))
+        K, H = model.fc.weight.shape
+        return dict(blocks=blocks, head=(off('fc.weight'), int(H), int(K)))
+
+    def mlp_eps(self):
+        """the eps of the MLP's BatchNorm layers (one value, or None)"""
+        eps = set(blk[1].eps for blk in self.base.model.layers)
+        return eps.pop() if len(eps) == 1 else None
+
+    def mlp_batched_blockers(self):
+        """Why this pack's rounds cannot run through ops.mlp_local_rounds: a
+        list of reasons, empty when they can."""
+        from fedtorch_amd.components.datasets.device_cache import \
+            DeviceCachedLoader
+        args, client = self.args, self.base
+        why = []
+        if not _BATCHED_MLP_ENABLED:
+            why.append('FEDTORCH_PACKED_BATCHED_MLP is not set')
+        layout = self.mlp_layout()
+        if layout is None:
+            why.append('model is not a plain MLP (no noise, BatchNorm on '
+                       'batch statistics, Dropout p = 0) that fills the '
+                       'arena')
+        elif self.mlp_eps() is None:
+            why.append('BatchNorm layers differ in eps')
+        if getattr(client.arena, 'half_flat', None) is not None \
+                or getattr(args, 'bf16', False):
+            why.append('bf16 compute')
+        if getattr(args, 'federated_type', None) != 'fedavg':
+            why.append('federated_type is not fedavg')
+        opt = client.optimizer
+        if getattr(opt, '_prox_mu', 0.0) != 0.0 or any(
+                getattr(opt, a, None) is not None
+                for a in ('_server', '_ctrl_server', '_ctrl_client',
+                          '_delta')):
+            why.append('a gradient correction is bound on the optimizer')
+        if getattr(args, 'federated_sync_type', None) != 'local_step':
+            why.append('federated_sync_type is not local_step')
+        if getattr(args, 'growing_batch_size', False):
+            why.append('growing_batch_size')
+        loaders = self.train_loaders
+        if not all(isinstance(l, DeviceCachedLoader) and not l._aug
+                   for l in loaders):
+            why.append('a local loader is not an un-augmented '
+                       'DeviceCachedLoader')
+        else:
+            B = loaders[0].batch_size
+            if any(l.batch_size != B for l in loaders):
+                why.append('batch sizes differ between clients')
+            elif not 2 <= B <= ops.MLPROUND_MAXB:
+                why.append('batch size %d outside 2 .. %d'
+                           % (B, ops.MLPROUND_MAXB))
+            # the slot loop's `break` on a 1-sample batch is not reproduced
+            if any(not l.drop_last and len(l.x) % l.batch_size == 1
+                   for l in loaders):
+                why.append('a partition leaves a 1-sample last batch')
+            if any(l.y.is_floating_point() for l in loaders):
+                why.append('class labels are not integers')
+            if layout is not None:
+                F = layout['blocks'][0][4]
+                if any(l.x[0].numel() != F for l in loaders):
+                    why.append('loader rows do not have %d features' % F)
+                if layout['head'][2] > ops.MLPROUND_MAXK:
+                    why.append('K=%d classes (K <= %d)'
+                               % (layout['head'][2], ops.MLPROUND_MAXK))
+                if len(layout['blocks']) > ops.MLPROUND_MAXL:
+                    why.append('%d blocks (L <= %d)'
+                               % (len(layout['blocks']), ops.MLPROUND_MAXL))
+        return why
+
+    def mlp_batched_eligible(self):
+        return not self.mlp_batched_blockers()
 
     def stacked_data(self):
         """(X [M, F] fp32, Y [M] int32 labels | fp32 targets, offsets [C+1]):

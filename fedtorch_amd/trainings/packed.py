@@ -96,19 +96,16 @@ def _apply_aggregate(client, server_flat, agg):
         client.work['srv_out_init'] = True
 
 
-def _batched_local_rounds(client, pack, server, online, snap, k_cut):
-    """The local steps of ALL online local clients of a linear model in one
-    ops.linear_local_rounds call (FEDTORCH_PACKED_BATCHED,
-    `ClientPack.batched_eligible`).
-
-    The host first walks the counters exactly as the slot loop does, client
-    by client and step by step, with no GPU work: local_index,
-    local_data_seen, epoch, the scheduled lr and the sync test, pulling each
-    step's rows from the loader's index_batches() (a fresh epoch whenever one
-    runs out, like the `while` / `for` pair of `_local_steps_fn`).  `snap`:
-    DRFA's [C, N] snapshot arena, row j receives client j's parameters before
-    its step `k_cut`.  Returns (loss [C, T], steps per client, lr of each
-    client's last step)."""
+def _plan_local_rounds(client, pack, online):
+    """The host's walk of a batched round, shared by the linear and the MLP
+    path: the counters exactly as the slot loop moves them, client by client
+    and step by step, with no GPU work: local_index, local_data_seen, epoch,
+    the scheduled lr and the sync test, pulling each step's rows from the
+    loader's index_batches() (a fresh epoch whenever one runs out, like the
+    `while` / `for` pair of `_local_steps_fn`).  Returns (plan, idx [C, T, B]
+    int32 rows of the stacked data, -1 = padding, lr [C, T], steps [C]) on
+    the host; plan[j] is None for an offline client, else its list of
+    (rows, lr)."""
     args = client.args
     _X, _Y, offs = pack.stacked_data()
     plan = [None] * pack.C
@@ -140,28 +137,53 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut):
         for s, (rows, lr_s) in enumerate(p):
             idx[j, s, :len(rows)] = rows + offs[j]
             lr[j, s] = lr_s
+    return plan, idx, lr, steps
+
+
+def _batched_local_rounds(client, pack, server, online, snap, k_cut,
+                          mlp=False):
+    """The local steps of ALL online local clients in one batched op call:
+    ops.linear_local_rounds for a linear model (FEDTORCH_PACKED_BATCHED,
+    `ClientPack.batched_eligible`), ops.mlp_local_rounds for an MLP
+    (`mlp=True`: FEDTORCH_PACKED_BATCHED_MLP,
+    `ClientPack.mlp_batched_eligible`).
+
+    The host first walks the counters (`_plan_local_rounds`).  `snap`:
+    DRFA's [C, N] snapshot arena, row j receives client j's parameters before
+    its step `k_cut`.  Returns (loss [C, T], steps per client, lr of each
+    client's last step)."""
+    args = client.args
+    _X, _Y, _offs = pack.stacked_data()
+    plan, idx, lr, steps = _plan_local_rounds(client, pack, online)
     g = client.optimizer.param_groups[0]
     momentum = g['in_momentum'] if args.in_momentum else 0.0
     dev = server.device
     mom_init = torch.tensor([int(b) for b in pack.mom_init],
                             dtype=torch.int32).to(dev)
-    w_off, b_off, K, _F = pack.linear_layout()
-    from fedtorch_amd.components.models.convex import LeastSquare
-    corr = {}
-    if args.federated_type == 'fedgate':
-        corr['delta'] = pack.delta
-    elif args.federated_type == 'scaffold':
-        corr.update(ctrl_server=client.model_server_control,
-                    ctrl_client=pack.ctrl)
-    elif args.federated_type == 'fedprox':
-        corr['prox_mu'] = args.fedprox_mu
-    loss = ops.linear_local_rounds(
-        _X, _Y, idx.to(dev), steps.to(dev), lr.to(dev), server,
-        pack.replicas, pack.in_mom if momentum != 0 else None, mom_init,
-        snap, k_cut, w_off=w_off, b_off=b_off, K=K,
-        loss_kind=1 if isinstance(client.model, LeastSquare) else 0,
-        weight_decay=g['weight_decay'], momentum=momentum,
-        dampening=g['dampening'], nesterov=g['nesterov'], **corr)
+    operands = (_X, _Y, idx.to(dev), steps.to(dev), lr.to(dev), server,
+                pack.replicas, pack.in_mom if momentum != 0 else None,
+                mom_init, snap, k_cut)
+    sgd = dict(weight_decay=g['weight_decay'], momentum=momentum,
+               dampening=g['dampening'], nesterov=g['nesterov'])
+    if mlp:
+        loss = ops.mlp_local_rounds(
+            *operands, layout=pack.mlp_layout(), eps=pack.mlp_eps(),
+            wd_numel=client.arena.wd_numel, **sgd)
+    else:
+        w_off, b_off, K, _F = pack.linear_layout()
+        from fedtorch_amd.components.models.convex import LeastSquare
+        corr = {}
+        if args.federated_type == 'fedgate':
+            corr['delta'] = pack.delta
+        elif args.federated_type == 'scaffold':
+            corr.update(ctrl_server=client.model_server_control,
+                        ctrl_client=pack.ctrl)
+        elif args.federated_type == 'fedprox':
+            corr['prox_mu'] = args.fedprox_mu
+        loss = ops.linear_local_rounds(
+            *operands, w_off=w_off, b_off=b_off, K=K,
+            loss_kind=1 if isinstance(client.model, LeastSquare) else 0,
+            **sgd, **corr)
     if pack.in_mom is not None:
         for j, p in enumerate(plan):
             if p:
@@ -209,9 +231,15 @@ def train_and_validate_federated_packed(client, pack, validate=False):
     # linear models: one launch for all clients' local steps instead of the
     # slot loop (off unless FEDTORCH_PACKED_BATCHED=1 and the pack qualifies)
     batched = pack.batched_eligible()
+    # MLP: the clients' steps batched per layer (off unless
+    # FEDTORCH_PACKED_BATCHED_MLP=1 and the pack qualifies)
+    batched_mlp = not batched and pack.mlp_batched_eligible()
     log('packed local steps: {}'.format(
-        'one batched launch per round' if batched else 'slot loop'),
+        'one batched launch per round' if batched
+        else 'MLP layers batched over the clients' if batched_mlp
+        else 'slot loop'),
         args.debug)
+    batched = batched or batched_mlp
     run_client = (lambda j, server_flat, fn: None) if batched \
         else pack.run_client
     if ftype == 'scaffold':
@@ -290,7 +318,7 @@ def train_and_validate_federated_packed(client, pack, validate=False):
         if batched:
             _loss, taus, lrs = _batched_local_rounds(
                 client, pack, server, online, kth if drfa else None,
-                k_cut if drfa else 0)
+                k_cut if drfa else 0, mlp=batched_mlp)
 
         partial = pack.accumulate_partial(server, weights)
         if ftype == 'scaffold':
