@@ -530,7 +530,9 @@ def _mlp_layout_check(layout, F, N):
 
 def mlp_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
                      mom_init, snap, k_cut, *, layout, eps, wd_numel,
-                     weight_decay, momentum, dampening, nesterov):
+                     weight_decay, momentum, dampening, nesterov,
+                     delta=None, ctrl_server=None, ctrl_client=None,
+                     prox_mu=0.0):
     """All local SGD steps of a round, for every packed client of an MLP
     (`components/models/mlp.py` without noise), batched per layer.
 
@@ -556,19 +558,30 @@ def mlp_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
         xh = (z - mu) rsqrt(var + eps) ; y_i = g_i xh + beta_i
         a_{i+1} = max(y_i, 0)
         logits = a_L Wfc^T ; loss[c, s] = mean CE(logits, Y[r])
-        backward of exactly that ; d = grad (+ wd p for arena index
-        < wd_numel) ; momentum / dampening / nesterov / first use
+        backward of exactly that ; d = grad ; [delta] d -= delta[c] ;
+        [control pair] d += ctrl_server - ctrl_client[c] ;
+        [prox_mu] d += prox_mu (p - server) ; d += wd p for arena index
+        < wd_numel ; momentum / dampening / nesterov / first use
         (mom_init[c] == 0 at s == 0: buf = d) ; p -= lr[c, s] d
-        -- the local branch of `fused_sgd_step`, in place in replicas[c]
-        (and in_mom[c])
+        -- the local branch of `fused_sgd_step` with its gradient
+        corrections, in place in replicas[c] (and in_mom[c])
       mom_init[c] <- 1 (with momentum)
 
-    Pad gaps of in_mom stay as they were; in_mom / mom_init are touched only
+    delta [C, N], or the pair ctrl_server [N] / ctrl_client [C, N], and
+    prox_mu >= 0 are constant over the call; only the parameter elements of
+    the correction rows of clients with steps > 0 are read.  Pad gaps of in_mom stay as they were; in_mom / mom_init are touched only
     when momentum != 0.  Returns loss [C, T]: the mean loss of each executed
     step, 0 elsewhere.  The eager twin raises ValueError for an executed
     step with fewer than 2 valid rows; the HIP path cannot see a device idx
     and stays in bounds and finite there (n = 1 gives xh = 0)."""
     dev = X.device
+    if (ctrl_server is None) != (ctrl_client is None):
+        raise RuntimeError('mlp_local_rounds: ctrl_server and ctrl_client '
+                           'come as a pair')
+    if delta is not None and ctrl_server is not None:
+        raise RuntimeError('mlp_local_rounds: delta and a control pair '
+                           'together are not supported (one correction '
+                           'vector per client)')
     if in_mom is None:
         in_mom = torch.empty(0, device=dev)
     if snap is None:
@@ -578,13 +591,20 @@ def mlp_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
             X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap,
             int(k_cut), _mlp_layout_flat(layout), float(eps), int(wd_numel),
             float(weight_decay), float(momentum), float(dampening),
-            bool(nesterov))
+            bool(nesterov),
+            delta if delta is not None else torch.empty(0, device=dev),
+            ctrl_server if ctrl_server is not None
+            else torch.empty(0, device=dev),
+            ctrl_client if ctrl_client is not None
+            else torch.empty(0, device=dev),
+            float(prox_mu))
 
     # eager twin: a per-client, per-step loop; the gradients come from
     # autograd over F.linear / F.batch_norm / F.relu / F.cross_entropy, the
     # update from the fused-SGD twin above over the whole row — the ops of
     # the packed slot loop, in its order.  Pad gaps (zero in a real arena,
-    # where the whole-row update leaves them zero) are put back afterwards.
+    # where the whole-row update leaves them zero) are put back afterwards;
+    # those of the correction rows are masked, never used.
     import torch.nn.functional as Fn
     C, T, B = idx.shape
     N = server.numel()
@@ -595,6 +615,9 @@ def mlp_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
     if k_cut < 0:
         raise ValueError('mlp_local_rounds: k_cut is %d, expected >= 0'
                          % k_cut)
+    if not (0 <= prox_mu < float('inf')):
+        raise ValueError('mlp_local_rounds: prox_mu must be finite and >= 0, '
+                         'got %r' % (prox_mu,))
     n_steps = steps.tolist()
     if max(n_steps) > T:
         raise ValueError('mlp_local_rounds: steps holds %d but idx has T=%d'
@@ -616,11 +639,19 @@ def mlp_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
         shapes += [(w, (out, fin)), (b, (out,)), (g, (out,)), (be, (out,))]
     fc, H, K = layout['head']
     shapes.append((fc, (K, H)))
+    zero = torch.zeros_like(server)
+    live = lambda t: torch.where(gap, zero, t)  # noqa: E731
     for c in range(C):
         if n_steps[c] <= 0:
             continue
         p = server.clone()
         grad = torch.zeros_like(p)
+        corr = dict(prox_mu=prox_mu, server=server if prox_mu != 0 else None)
+        if delta is not None:
+            corr['delta'] = live(delta[c])
+        if ctrl_server is not None:
+            corr.update(ctrl_server=live(ctrl_server),
+                        ctrl_client=live(ctrl_client[c]))
         mom_gaps = in_mom[c][gap].clone() if use_mom else None
         for s in range(n_steps[c]):
             if snap.numel() and s + 1 == k_cut:
@@ -653,7 +684,8 @@ def mlp_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
                 apply_lr=True, apply_in_momentum=use_mom,
                 apply_out_momentum=False,
                 in_buf=in_mom[c] if use_mom else None,
-                first_in=use_mom and not inits[c], wd_numel=wd_numel)
+                first_in=use_mom and not inits[c], wd_numel=wd_numel,
+                **corr)
             if use_mom:
                 inits[c] = 1
         replicas[c].copy_(torch.where(gap, server, p))

@@ -18,6 +18,9 @@
 //         da = dz_M M ; dM = dz_M^T a ; SGD on M ; BN backward -> dz_i ;
 //         SGD on g_i, beta_i, b_i
 //       dW_0 = dz_0^T x ; SGD on W_0                         mlp_bwd_k<true>
+//       every SGD update with fused_sgd_step's gradient corrections:
+//         d = g ; [delta] d -= delta[c] ; [control pair] d += c - c_c[c] ;
+//         [prox_mu] d += mu (p - server) ; then wd, momentum, p -= lr d
 //     mom_init[c] <- 1 (with momentum)                       mlp_rows_k(2)
 //
 // 2L + 2 launches per step, grid = (C, column tiles), 256 threads.  Every
@@ -42,6 +45,14 @@
 // >= M) are never dereferenced: their rows are zero in every staged tile,
 // in xh, a and dz, and they are excluded from n.  Only parameter elements of
 // the rows of online clients are written (replicas: the whole row first).
+//
+// A gradient correction is constant over the round and is read where it is
+// used: lanes run along the contiguous arena index at every update site, so
+// its loads coalesce like the momentum's, and they are issued ahead of the
+// sums that precede the update.  The backward kernels exist twice
+// (template <bool CORR>): without a correction the launcher runs code that
+// knows none.  Only parameter elements of the correction rows of clients
+// with steps > 0 are read, and none past the client's last step.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.h"
@@ -52,6 +63,10 @@
 #define MLPROUND_MAXL 8
 #define MLP_TN 32               // columns of a tile, and depth of a chunk
 #define MLP_LD 33               // LDS row stride of a tile
+// gradient corrections of a round (MlpRoundArgs.corr, the same in all blocks)
+#define MLPROUND_DELTA 1
+#define MLPROUND_CTRL 2
+#define MLPROUND_PROX 4
 
 struct MlpLayout {
   int L;
@@ -78,9 +93,13 @@ struct MlpRoundArgs {
   float* snap;           // [C, N] or null
   float* loss;           // [C, T]
   float* ws;             // [C, ws_stride]
+  const float* corr_rows;  // [C, N] or null: delta (d -= delta[c]) or, with
+  const float* ctrl_s;     // ctrl_s [N], the client controls (d += c - c_c[c])
   int M, B, T, N;
   int k_cut, use_mom, nesterov, wd_numel;
   float wd, mom, omd, eps;
+  float prox_mu;         // != 0: d += prox_mu (p - server)
+  int corr;              // MLPROUND_DELTA | _CTRL | _PROX, 0: no correction
   MlpLayout lay;
 };
 
@@ -90,8 +109,15 @@ struct MlpSgd {
   int use_mom, nesterov, wd_numel;
   float* p;              // the client's replica row
   float* m;              // its momentum row
+  // the correction (set and used by the CORR kernels only)
+  const float* cr;       // the client's correction row
+  const float* cs;       // the server control
+  const float* srv;      // the server
+  float prox_mu;
+  int corr;
 };
 
+template <bool CORR>
 __device__ __forceinline__ MlpSgd mlp_sgd(const MlpRoundArgs& a, int c,
                                           int s) {
   MlpSgd u;
@@ -106,12 +132,43 @@ __device__ __forceinline__ MlpSgd mlp_sgd(const MlpRoundArgs& a, int c,
   u.wd_numel = a.wd_numel;
   u.p = a.replicas + (long)c * a.N;
   u.m = a.use_mom ? a.in_mom + (long)c * a.N : nullptr;
+  if (CORR) {
+    u.cr = a.corr_rows ? a.corr_rows + (long)c * a.N : nullptr;
+    u.cs = a.ctrl_s;
+    u.srv = a.server;
+    u.prox_mu = a.prox_mu;
+    u.corr = a.corr;
+  }
   return u;
 }
 
+// the correction of arena element e: cv = delta or c - c_c (the difference
+// first, as fused_sgd_step forms it), sv = the server's value for the
+// proximal term.  Loaded ahead of the update that uses it.
+struct MlpCorr {
+  float cv, sv;
+};
+
+template <bool CORR>
+__device__ __forceinline__ MlpCorr mlp_corr_load(const MlpSgd& u, int e) {
+  MlpCorr k = {0.f, 0.f};
+  if (CORR) {
+    if (u.corr & MLPROUND_DELTA) k.cv = u.cr[e];
+    else if (u.corr & MLPROUND_CTRL) k.cv = u.cs[e] - u.cr[e];
+    if (u.corr & MLPROUND_PROX) k.sv = u.srv[e];
+  }
+  return k;
+}
+
 // the local branch of fused_sgd_step on arena element e, p its value
+template <bool CORR>
 __device__ __forceinline__ void mlp_update(const MlpSgd& u, int e, float p,
-                                           float g) {
+                                           float g, const MlpCorr& k) {
+  if (CORR) {
+    if (u.corr & MLPROUND_DELTA) g -= k.cv;
+    else if (u.corr & MLPROUND_CTRL) g += k.cv;
+    if (u.corr & MLPROUND_PROX) g = fmaf(u.prox_mu, p - k.sv, g);
+  }
   float d = e < u.wd_numel ? fmaf(u.wd, p, g) : g;
   if (u.use_mom) {
     const float bu = fmaf(u.mom, u.m[e], u.omd * d);
@@ -363,7 +420,8 @@ mlp_head_k(const MlpRoundArgs a, int s) {
 //           M[:, tile], BN backward, SGD on g, beta, b, dz_li[:, tile].
 //   FIRST   tile of the input features; M = W_0 [nO, ncol = F]; a = x
 //           re-gathered; SGD on W_0[:, tile] only.
-template <bool FIRST>
+// CORR: the SGD updates take the round's gradient correction.
+template <bool FIRST, bool CORR>
 __global__ void __launch_bounds__(MLPROUND_THREADS)
 mlp_bwd_k(const MlpRoundArgs a, int s, int li) {
   __shared__ float As[MLPROUND_MAXB * MLP_LD];   // dz_M chunk, later dy
@@ -378,7 +436,7 @@ mlp_bwd_k(const MlpRoundArgs a, int s, int li) {
   const int j0 = blockIdx.y * MLP_TN;
   const int n = mlp_rows(a, c, s, rid);
   const int L = a.lay.L;
-  const MlpSgd u = mlp_sgd(a, c, s);
+  const MlpSgd u = mlp_sgd<CORR>(a, c, s);
   float* ws = a.ws + (long)c * a.lay.ws_stride;
   const int ncol = FIRST ? a.lay.in[0] : a.lay.out[li];
   const bool head = !FIRST && li == L - 1;
@@ -398,6 +456,16 @@ mlp_bwd_k(const MlpRoundArgs a, int s, int li) {
   for (int o0 = 0; o0 < nO; o0 += MLP_TN) {
     mlp_load_a<false>(As, dzM, nO, o0, nO, rid);
     mlp_load_w<true>(Ws, u.p + m_off, j0, ncol, o0, nO);
+    // the correction of the chunk's elements: issued here, used after the
+    // rows
+    MlpCorr kc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int oo = ty + 8 * q;
+      kc[q] = MlpCorr{0.f, 0.f};
+      if (cin && o0 + oo < nO)
+        kc[q] = mlp_corr_load<CORR>(u, m_off + (o0 + oo) * ncol + col);
+    }
     __syncthreads();
     if (!FIRST) mlp_fma_tile(acc, As, Ws);
     // weight gradient of M[o0 + oo][col], oo = ty + 8 q, rows in order
@@ -412,8 +480,8 @@ mlp_bwd_k(const MlpRoundArgs a, int s, int li) {
     for (int q = 0; q < 4; ++q) {
       const int oo = ty + 8 * q;
       if (cin && o0 + oo < nO)
-        mlp_update(u, m_off + (o0 + oo) * ncol + col, Ws[tx * MLP_LD + oo],
-                   g[q]);
+        mlp_update<CORR>(u, m_off + (o0 + oo) * ncol + col,
+                         Ws[tx * MLP_LD + oo], g[q], kc[q]);
     }
     __syncthreads();
   }
@@ -432,6 +500,12 @@ mlp_bwd_k(const MlpRoundArgs a, int s, int li) {
   __syncthreads();
   const float nf = (float)n;
   if (tid < MLP_TN) {
+    // the corrections of gamma and beta: issued ahead of the sums
+    MlpCorr kg = {0.f, 0.f}, kb = {0.f, 0.f};
+    if (j0 + tid < out) {
+      kg = mlp_corr_load<CORR>(u, a.lay.g[li] + j0 + tid);
+      kb = mlp_corr_load<CORR>(u, a.lay.be[li] + j0 + tid);
+    }
     float s1 = 0.f, s2 = 0.f;
     for (int b = 0; b < a.B; ++b) {
       const float d = As[b * MLP_LD + tid];
@@ -445,8 +519,8 @@ mlp_bwd_k(const MlpRoundArgs a, int s, int li) {
     if (cj < out) {
       const float gam = u.p[a.lay.g[li] + cj];
       coef = gam * ws[a.lay.rstd[li] + cj] * (n > 0 ? 1.f / nf : 0.f);
-      mlp_update(u, a.lay.g[li] + cj, gam, s2);
-      mlp_update(u, a.lay.be[li] + cj, u.p[a.lay.be[li] + cj], s1);
+      mlp_update<CORR>(u, a.lay.g[li] + cj, gam, s2, kg);
+      mlp_update<CORR>(u, a.lay.be[li] + cj, u.p[a.lay.be[li] + cj], s1, kb);
     }
     st[2 * MLP_TN + tid] = coef;
   }
@@ -469,9 +543,10 @@ mlp_bwd_k(const MlpRoundArgs a, int s, int li) {
   for (int m = 0; m < 8; ++m) As[(ty + 8 * m) * MLP_LD + tx] = dy[m];
   __syncthreads();
   if (tid < MLP_TN && j0 + tid < out) {  // db = sum of dz over the rows
+    const int e = a.lay.b[li] + j0 + tid;
+    const MlpCorr kc = mlp_corr_load<CORR>(u, e);
     float sb = 0.f;
     for (int b = 0; b < a.B; ++b) sb += As[b * MLP_LD + tid];
-    const int e = a.lay.b[li] + j0 + tid;
-    mlp_update(u, e, u.p[e], sb);
+    mlp_update<CORR>(u, e, u.p[e], sb, kc);
   }
 }

@@ -2649,7 +2649,9 @@ torch::Tensor mlp_local_rounds(
     torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,
     torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,
     long k_cut, std::vector<int64_t> layout, double eps, long wd_numel,
-    double weight_decay, double momentum, double dampening, bool nesterov) {
+    double weight_decay, double momentum, double dampening, bool nesterov,
+    torch::Tensor delta, torch::Tensor ctrl_server, torch::Tensor ctrl_client,
+    double prox_mu) {
   const char* who = "mlp_local_rounds";
   TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous(), who,
               ": X must be contiguous [M, F] on GPU");
@@ -2680,6 +2682,24 @@ torch::Tensor mlp_local_rounds(
     linround_check(who, "in_mom", in_mom, torch::kFloat, {C, N}, dev);
   const bool has_snap = snap.numel() != 0;
   if (has_snap) linround_check(who, "snap", snap, torch::kFloat, {C, N}, dev);
+  // the gradient correction of the round (an empty tensor: none)
+  const bool has_delta = delta.numel() != 0;
+  const bool has_cs = ctrl_server.numel() != 0;
+  const bool has_cc = ctrl_client.numel() != 0;
+  TORCH_CHECK(has_cs == has_cc, who, ": ctrl_server and ctrl_client come as "
+              "a pair, got only ", has_cs ? "ctrl_server" : "ctrl_client");
+  TORCH_CHECK(!(has_delta && has_cs), who, ": delta and a control pair "
+              "together are not supported (one correction vector per "
+              "client)");
+  if (has_delta)
+    linround_check(who, "delta", delta, torch::kFloat, {C, N}, dev);
+  if (has_cs) {
+    linround_check(who, "ctrl_server", ctrl_server, torch::kFloat, {N}, dev);
+    linround_check(who, "ctrl_client", ctrl_client, torch::kFloat, {C, N},
+                   dev);
+  }
+  TORCH_CHECK(std::isfinite(prox_mu) && prox_mu >= 0.0, who,
+              ": prox_mu must be finite and >= 0, got ", prox_mu);
   TORCH_CHECK(k_cut >= 0, who, ": k_cut is ", k_cut, ", expected >= 0");
   TORCH_CHECK(!nesterov || (use_mom && dampening == 0.0), who,
               ": nesterov needs a momentum and zero dampening");
@@ -2776,6 +2796,13 @@ torch::Tensor mlp_local_rounds(
   a.use_mom = use_mom; a.nesterov = nesterov; a.wd_numel = (int)wd_numel;
   a.wd = (float)weight_decay; a.mom = (float)momentum;
   a.omd = (float)(1.0 - dampening); a.eps = (float)eps;
+  a.corr_rows = has_delta ? delta.data_ptr<float>()
+                : has_cs  ? ctrl_client.data_ptr<float>()
+                          : nullptr;
+  a.ctrl_s = has_cs ? ctrl_server.data_ptr<float>() : nullptr;
+  a.prox_mu = (float)prox_mu;
+  a.corr = (has_delta ? MLPROUND_DELTA : 0) | (has_cs ? MLPROUND_CTRL : 0) |
+           (prox_mu != 0.0 ? MLPROUND_PROX : 0);
   a.lay = lay;
 
   const dim3 blk(MLPROUND_THREADS);
@@ -2794,11 +2821,23 @@ torch::Tensor mlp_local_rounds(
       hipLaunchKernelGGL(mlp_fwd_layer_k<false>, dim3(Cu, tiles(lay.out[i])),
                          blk, 0, STREAM, a, s, i);
     hipLaunchKernelGGL(mlp_head_k, dim3(Cu), blk, 0, STREAM, a, s);
-    for (int i = (int)L - 1; i >= 0; --i)
-      hipLaunchKernelGGL(mlp_bwd_k<false>, dim3(Cu, tiles(lay.out[i])), blk,
-                         0, STREAM, a, s, i);
-    hipLaunchKernelGGL(mlp_bwd_k<true>, dim3(Cu, tiles(lay.in[0])), blk, 0,
-                       STREAM, a, s, 0);
+    // without a correction: the kernels that know none
+    for (int i = (int)L - 1; i >= 0; --i) {
+      if (a.corr)
+        hipLaunchKernelGGL((mlp_bwd_k<false, true>),
+                           dim3(Cu, tiles(lay.out[i])), blk, 0, STREAM, a, s,
+                           i);
+      else
+        hipLaunchKernelGGL((mlp_bwd_k<false, false>),
+                           dim3(Cu, tiles(lay.out[i])), blk, 0, STREAM, a, s,
+                           i);
+    }
+    if (a.corr)
+      hipLaunchKernelGGL((mlp_bwd_k<true, true>), dim3(Cu, tiles(lay.in[0])),
+                         blk, 0, STREAM, a, s, 0);
+    else
+      hipLaunchKernelGGL((mlp_bwd_k<true, false>), dim3(Cu, tiles(lay.in[0])),
+                         blk, 0, STREAM, a, s, 0);
   }
   if (use_mom)
     hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, 1), blk, 0, STREAM, a, 2);

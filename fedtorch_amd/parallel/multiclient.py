@@ -39,6 +39,11 @@ _BATCHED_CORR_ENABLED = \
 # ``FEDTORCH_PACKED_BATCHED_MLP=1``; timings in profiles/packed_mlp_notes.md.
 _BATCHED_MLP_ENABLED = \
     os.environ.get('FEDTORCH_PACKED_BATCHED_MLP', '0') == '1'
+# The same batched kernels for fedprox / scaffold / dense fedgate (their
+# gradient-correction term).  A second opt-in on top of the MLP one:
+# ``FEDTORCH_PACKED_BATCHED_MLP_CORR=1``.
+_BATCHED_MLP_CORR_ENABLED = \
+    os.environ.get('FEDTORCH_PACKED_BATCHED_MLP_CORR', '0') == '1'
 
 # federated types the packed trainer implements
 PACKED_TYPES = ('fedavg', 'fedprox', 'scaffold', 'fedgate')
@@ -178,12 +183,7 @@ class ClientPack(object):
         if getattr(client.arena, 'half_flat', None) is not None \
                 or getattr(args, 'bf16', False):
             why.append('bf16 compute')
-        t = getattr(args, 'federated_type', None)
-        corr_ok = _BATCHED_CORR_ENABLED \
-            and t in ('fedprox', 'scaffold', 'fedgate') \
-            and not (getattr(args, 'quantized', False)
-                     or getattr(args, 'compressed', False))
-        if t != 'fedavg' and not corr_ok:
+        if not self._batched_type_ok(_BATCHED_CORR_ENABLED):
             why.append('federated_type is not fedavg')
         opt = client.optimizer
         if getattr(opt, '_prox_mu', 0.0) != 0.0 or any(
@@ -230,6 +230,32 @@ class ClientPack(object):
 
     def batched_eligible(self):
         return not self.batched_blockers()
+
+    def _batched_type_ok(self, corr_enabled):
+        """fedavg always; fedprox / scaffold / dense fedgate when the path's
+        gradient-correction opt-in is on"""
+        args = self.args
+        t = getattr(args, 'federated_type', None)
+        if t == 'fedavg':
+            return True
+        return corr_enabled and t in ('fedprox', 'scaffold', 'fedgate') \
+            and not (getattr(args, 'quantized', False)
+                     or getattr(args, 'compressed', False))
+
+    def batched_correction(self):
+        """The gradient-correction operands of a batched round
+        (ops.linear_local_rounds / ops.mlp_local_rounds) for the pack's
+        federated type: what `arm_correction` binds client by client in the
+        slot loop, as [C, N] rows."""
+        t = getattr(self.args, 'federated_type', None)
+        if t == 'fedgate':
+            return dict(delta=self.delta)
+        if t == 'scaffold':
+            return dict(ctrl_server=self.base.model_server_control,
+                        ctrl_client=self.ctrl)
+        if t == 'fedprox':
+            return dict(prox_mu=self.args.fedprox_mu)
+        return {}
 
     # ---- batched round of an MLP (trainings/packed.py) ---------------------
     def mlp_layout(self):
@@ -293,7 +319,7 @@ class ClientPack(object):
         if getattr(client.arena, 'half_flat', None) is not None \
                 or getattr(args, 'bf16', False):
             why.append('bf16 compute')
-        if getattr(args, 'federated_type', None) != 'fedavg':
+        if not self._batched_type_ok(_BATCHED_MLP_CORR_ENABLED):
             why.append('federated_type is not fedavg')
         opt = client.optimizer
         if getattr(opt, '_prox_mu', 0.0) != 0.0 or any(

@@ -146,7 +146,8 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
     ops.linear_local_rounds for a linear model (FEDTORCH_PACKED_BATCHED,
     `ClientPack.batched_eligible`), ops.mlp_local_rounds for an MLP
     (`mlp=True`: FEDTORCH_PACKED_BATCHED_MLP,
-    `ClientPack.mlp_batched_eligible`).
+    `ClientPack.mlp_batched_eligible`), either with the gradient correction
+    of the federated type (`ClientPack.batched_correction`).
 
     The host first walks the counters (`_plan_local_rounds`).  `snap`:
     DRFA's [C, N] snapshot arena, row j receives client j's parameters before
@@ -165,21 +166,14 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
                 mom_init, snap, k_cut)
     sgd = dict(weight_decay=g['weight_decay'], momentum=momentum,
                dampening=g['dampening'], nesterov=g['nesterov'])
+    corr = pack.batched_correction()
     if mlp:
         loss = ops.mlp_local_rounds(
             *operands, layout=pack.mlp_layout(), eps=pack.mlp_eps(),
-            wd_numel=client.arena.wd_numel, **sgd)
+            wd_numel=client.arena.wd_numel, **sgd, **corr)
     else:
         w_off, b_off, K, _F = pack.linear_layout()
         from fedtorch_amd.components.models.convex import LeastSquare
-        corr = {}
-        if args.federated_type == 'fedgate':
-            corr['delta'] = pack.delta
-        elif args.federated_type == 'scaffold':
-            corr.update(ctrl_server=client.model_server_control,
-                        ctrl_client=pack.ctrl)
-        elif args.federated_type == 'fedprox':
-            corr['prox_mu'] = args.fedprox_mu
         loss = ops.linear_local_rounds(
             *operands, w_off=w_off, b_off=b_off, K=K,
             loss_kind=1 if isinstance(client.model, LeastSquare) else 0,

@@ -3,14 +3,17 @@
 (FEDTORCH_PACKED_BATCHED_MLP off: per client and step one eager forward,
 backward and fused SGD launch) against the batched round (on: the clients'
 steps batched per layer by ops.mlp_local_rounds, hip/mlpround.h).  Needs a
-GPU.
+GPU.  --federated_type fedprox | scaffold | fedgate times the same pair with
+the algorithm's gradient correction (FEDTORCH_PACKED_BATCHED_MLP_CORR: both
+flags on against both off).
 
 Configuration: the stock MLP (784-500-500-10) on synthetic MNIST, B = 50,
 tau = 10, C in {16, 128} virtual clients on one rank, every client online,
 momentum 0.9 (--momentum on,off for both).
 
 Per configuration ONE process builds the federation once, warms both paths
-up, then runs --rounds rounds of each path ALTERNATELY; a round is timed
+up (at least two rounds each, so that delta and the controls are non-zero in
+the timed rounds), then runs --rounds rounds of each path ALTERNATELY; a round is timed
 wall-clock between two device synchronisations (it includes the host's plan
 walk, the aggregation and the replica re-sync, which both paths share).  The
 range of each path is printed so the spread is visible.  The loaders, the
@@ -33,7 +36,10 @@ from fedtorch_amd.parallel import multiclient  # noqa: E402
 B, TAU = 50, 10
 
 
-def federation(C, momentum, hidden, layers):
+TYPES = ('fedavg', 'fedprox', 'scaffold', 'fedgate')
+
+
+def federation(C, momentum, hidden, layers, ftype='fedavg'):
     from fedtorch_amd.parameters import get_args
     from fedtorch_amd.nodes import Client
     os.environ['FEDTORCH_SYNTH_SIZE'] = str(C * 500)
@@ -41,7 +47,7 @@ def federation(C, momentum, hidden, layers):
     np.random.seed(1)
     argv = ['-d', 'mnist', '-a', 'mlp', '--mlp_hidden_size', str(hidden),
             '--mlp_num_layers', str(layers), '-f', 'true',
-            '--federated_type', 'fedavg', '--num_comms', '1',
+            '--federated_type', ftype, '--num_comms', '1',
             '--clients_per_rank', str(C), '-b', str(B), '--lr', '0.05',
             '--federated_sync_type', 'local_step', '--local_step', str(TAU),
             '--online_client_rate', '1.0',
@@ -74,6 +80,7 @@ def one_round(client, pack, batched):
     from fedtorch_amd.trainings.packed import \
         train_and_validate_federated_packed
     multiclient._BATCHED_MLP_ENABLED = batched
+    multiclient._BATCHED_MLP_CORR_ENABLED = batched
     assert pack.mlp_batched_eligible() == batched, pack.mlp_batched_blockers()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -99,7 +106,9 @@ def profile_round(client, pack):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=3)
-    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--federated_type', type=str, default='fedavg',
+                    choices=TYPES)
     ap.add_argument('--clients', type=str, default='16,128')
     ap.add_argument('--momentum', type=str, default='on')
     ap.add_argument('--hidden', type=int, default=500)
@@ -109,15 +118,19 @@ def main():
     if not (torch.cuda.is_available() and ops.hip_available()):
         raise SystemExit('packed_mlp_micro needs a GPU and the built kernel '
                          'pack')
-    old = multiclient._BATCHED_MLP_ENABLED
+    old = (multiclient._BATCHED_MLP_ENABLED,
+           multiclient._BATCHED_MLP_CORR_ENABLED)
+    ftype = a.federated_type
     try:
         for C in [int(c) for c in a.clients.split(',')]:
             for momentum in [m == 'on' for m in a.momentum.split(',')]:
-                tag = 'mlp 784-%s-10 C=%d momentum=%s' % (
-                    '-'.join([str(a.hidden)] * a.layers), C,
+                tag = 'mlp 784-%s-10 %s C=%d momentum=%s' % (
+                    '-'.join([str(a.hidden)] * a.layers), ftype, C,
                     'on' if momentum else 'off')
-                client, pack = federation(C, momentum, a.hidden, a.layers)
-                for _ in range(a.warmup):
+                client, pack = federation(C, momentum, a.hidden, a.layers,
+                                          ftype)
+                # two rounds at least: the first one's correction is zero
+                for _ in range(max(a.warmup, 2)):
                     for batched in (False, True):
                         one_round(client, pack, batched)
                 t = {False: [], True: []}
@@ -135,10 +148,15 @@ def main():
                           else 'overlap',
                           statistics.median(s) / statistics.median(f)),
                       flush=True)
+                for name, rows in (('delta', pack.delta),
+                                   ('ctrl', pack.ctrl)):
+                    if rows is not None:
+                        assert bool(rows.any()), name + ' is still zero'
                 if a.profile:
                     profile_round(client, pack)
     finally:
-        multiclient._BATCHED_MLP_ENABLED = old
+        (multiclient._BATCHED_MLP_ENABLED,
+         multiclient._BATCHED_MLP_CORR_ENABLED) = old
     print('PACKED_MLP_MICRO_OK')
 
 
