@@ -696,6 +696,267 @@ def mlp_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
 
 
 # --------------------------------------------------------------------------
+# packed CNN: all clients' local steps batched per layer (hip/cnnround.h)
+# --------------------------------------------------------------------------
+
+# kept equal to the CNNROUND_MAX* of hip/cnnround.h (a GPU test compares)
+CNNROUND_MAXB = 64
+CNNROUND_MAXK = 128
+CNNROUND_MAXCIN = 4
+CNNROUND_MAXS = 32
+CNNROUND_MAXC1 = 24
+CNNROUND_MAXC2 = 64
+CNNROUND_MAXH = 4096
+
+
+def cnn_round_limits():
+    """the largest B, K, Cin, S, C1, C2, H of ops.cnn_local_rounds"""
+    return dict(B=CNNROUND_MAXB, K=CNNROUND_MAXK, Cin=CNNROUND_MAXCIN,
+                S=CNNROUND_MAXS, C1=CNNROUND_MAXC1, C2=CNNROUND_MAXC2,
+                H=CNNROUND_MAXH)
+
+
+def _cnn_layout_flat(layout):
+    """[Cin, S, w1, b1, C1, nhwc1, w2, b2, C2, nhwc2, fw1, fb1, H, fw2, fb2,
+    K] of a layout dict"""
+    parts = [tuple(int(v) for v in layout[k])
+             for k in ('image', 'conv1', 'conv2', 'fc1', 'fc2')]
+    if [len(p) for p in parts] != [2, 4, 4, 3, 3]:
+        raise ValueError('cnn_local_rounds: a layout is image=(Cin, S), '
+                         'conv1 / conv2=(w_off, b_off, C, nhwc), fc1 / fc2='
+                         '(w_off, b_off, out)')
+    return [v for p in parts for v in p]
+
+
+def cnn_layout_check(layout, F, N):
+    """the launcher's layout checks (ValueError); returns the spans
+    [(start, end)] of the eight parameter tensors in the arena, in the order
+    conv1 w, b, conv2 w, b, fc1 w, b, fc2 w, b"""
+    who = 'cnn_local_rounds: '
+    (Cin, S, w1, b1, C1, n1, w2, b2, C2, n2, fw1, fb1, H, fw2, fb2,
+     K) = _cnn_layout_flat(layout)
+    if not (1 <= Cin <= CNNROUND_MAXCIN and 1 <= S <= CNNROUND_MAXS):
+        raise ValueError(who + 'unsupported image (Cin=%d, S=%d), 1 <= Cin '
+                         '<= %d, S <= %d' % (Cin, S, CNNROUND_MAXCIN,
+                                             CNNROUND_MAXS))
+    if S < 6 or (S - 4) % 2 or (S - 4) // 2 < 6 or ((S - 4) // 2 - 4) % 2:
+        raise ValueError(who + 'S=%d does not pool evenly twice (S - 4 and '
+                         '(S - 4) / 2 - 4 even, the last map at least 1x1)'
+                         % S)
+    S2 = ((S - 4) // 2 - 4) // 2
+    F2 = C2 * S2 * S2
+    if F != Cin * S * S:
+        raise ValueError(who + 'X has %d features, the image (%d, %d, %d) '
+                         'has %d' % (F, Cin, S, S, Cin * S * S))
+    if not (1 <= C1 <= CNNROUND_MAXC1 and 1 <= C2 <= CNNROUND_MAXC2
+            and 1 <= H <= CNNROUND_MAXH):
+        raise ValueError(who + 'unsupported C1=%d C2=%d H=%d (C1 <= %d, C2 '
+                         '<= %d, H <= %d)' % (C1, C2, H, CNNROUND_MAXC1,
+                                              CNNROUND_MAXC2, CNNROUND_MAXH))
+    if not 1 <= K <= CNNROUND_MAXK:
+        raise ValueError(who + 'unsupported K=%d (1 <= K <= %d)'
+                         % (K, CNNROUND_MAXK))
+    if n1 not in (0, 1) or n2 not in (0, 1):
+        raise ValueError(who + 'the nhwc flag of a conv must be 0 or 1')
+    spans = [(w1, w1 + C1 * Cin * 25), (b1, b1 + C1),
+             (w2, w2 + C2 * C1 * 25), (b2, b2 + C2),
+             (fw1, fw1 + H * F2), (fb1, fb1 + H),
+             (fw2, fw2 + K * H), (fb2, fb2 + K)]
+    for lo, hi in spans:
+        if lo < 0 or hi > N:
+            raise ValueError(who + 'layout tensor [%d, %d) does not fit the '
+                             'arena of %d' % (lo, hi, N))
+    order = sorted(spans)
+    for (_l0, h0), (l1, _h1) in zip(order, order[1:]):
+        if h0 > l1:
+            raise ValueError(who + 'layout tensors overlap at arena element '
+                             '%d' % l1)
+    return spans
+
+
+def cnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
+                     mom_init, snap, k_cut, *, layout, wd_numel,
+                     weight_decay, momentum, dampening, nesterov):
+    """All local SGD steps of a round, for every packed client of the
+    LeNet-style CNN of `components/models/cnn.py`, batched per layer.
+
+    X [M, Cin*S*S] f32, a row is one image in (c, h, w) order; Y [M] int32
+    class ids; idx [C, T, B] int32 rows of X per sample, -1 = padding,
+    1 <= B <= 64; steps [C] int32 (0 = offline, nothing of that client is
+    read or written); lr [C, T] f32; server [N]; replicas [C, N] (out);
+    in_mom [C, N] or None/empty; mom_init [C] int32 (in/out); snap [C, N] or
+    None/empty: parameters BEFORE step k_cut (1-based), written when
+    1 <= k_cut <= steps[c].
+
+    layout: dict(image=(Cin, S), conv1=(w_off, b_off, C1, nhwc),
+    conv2=(w_off, b_off, C2, nhwc), fc1=(w_off, b_off, H),
+    fc2=(w_off, b_off, K)): the arena offsets and shapes.  Kernel size 5,
+    stride 1, no padding and pool 2/2 are fixed.  `nhwc`: the conv weight's
+    elements sit in the arena as [co][kh][kw][ci] (a channels_last parameter,
+    `parallel/arena.py`), else as [co][ci][kh][kw].  Limits:
+    `cnn_round_limits()`; S - 4 and S1 - 4 even, S2 >= 1.
+
+    for every client c with steps[c] > 0:
+      replicas[c] <- server                    (whole row, pad gaps included)
+      for s in 0 .. steps[c]-1, rows r = idx[c, s, :] >= 0, n = #rows >= 1:
+        [snap[c] <- replicas[c]   if s + 1 == k_cut]
+        x  = X[r] as [n, Cin, S, S]
+        p1 = maxpool2(relu(conv5(x,  W1) + b1))    S1 = (S - 4) / 2
+        p2 = maxpool2(relu(conv5(p1, W2) + b2))    S2 = (S1 - 4) / 2
+        a  = relu(flat(p2) Wf1^T + bf1)            flat (c2 * S2 + h) * S2 + w
+        logits = a Wf2^T + bf2 ; loss[c, s] = mean CE(logits, Y[r])
+        backward of exactly that (pool: the first maximum of a window in
+        scan order; ReLU mask z > 0) ; d = grad ; d += wd p for arena index
+        < wd_numel ; momentum / dampening / nesterov / first use
+        (mom_init[c] == 0 at s == 0: buf = d) ; p -= lr[c, s] d
+        -- the local branch of `fused_sgd_step`, in place in replicas[c]
+        (and in_mom[c])
+      mom_init[c] <- 1 (with momentum)
+
+    Pad gaps of in_mom stay as they were; in_mom / mom_init are touched only
+    when momentum != 0.  Returns loss [C, T]: the mean loss of each executed
+    step, 0 elsewhere.  The eager twin raises ValueError for an executed
+    step with no valid row; the HIP path cannot see a device idx and stays
+    in bounds and finite there."""
+    dev = X.device
+    if in_mom is None:
+        in_mom = torch.empty(0, device=dev)
+    if snap is None:
+        snap = torch.empty(0, device=dev)
+    if _use_hip(X, server, replicas):
+        return _C.cnn_local_rounds(
+            X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap,
+            int(k_cut), _cnn_layout_flat(layout), int(wd_numel),
+            float(weight_decay), float(momentum), float(dampening),
+            bool(nesterov))
+
+    # eager twin: a per-client, per-step loop; the gradients come from
+    # autograd over F.conv2d / F.max_pool2d / F.relu / F.linear /
+    # F.cross_entropy, the update from the fused-SGD twin above over the
+    # whole row -- the ops of the packed slot loop, in its order.  Pad gaps
+    # (zero in a real arena, where the whole-row update leaves them zero) are
+    # put back afterwards.
+    import torch.nn.functional as Fn
+    who = 'cnn_local_rounds: '
+    for name, t, dt in (('X', X, torch.float32), ('Y', Y, torch.int32),
+                        ('idx', idx, torch.int32),
+                        ('steps', steps, torch.int32),
+                        ('lr', lr, torch.float32),
+                        ('server', server, torch.float32),
+                        ('replicas', replicas, torch.float32),
+                        ('mom_init', mom_init, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError(who + '%s must be contiguous %s on %s'
+                             % (name, dt, dev))
+    if X.dim() != 2 or idx.dim() != 3 or server.dim() != 1:
+        raise ValueError(who + 'X is [M, F], idx [C, T, B], server [N]')
+    C, T, B = idx.shape
+    N = server.numel()
+    M = X.shape[0]
+    use_mom = momentum != 0
+    for name, t in (('in_mom', in_mom if use_mom else None),
+                    ('snap', snap if snap.numel() else None)):
+        if t is not None and (t.dtype != torch.float32
+                              or not t.is_contiguous() or t.device != dev):
+            raise ValueError(who + '%s must be contiguous %s on %s'
+                             % (name, torch.float32, dev))
+    if nesterov and (not use_mom or dampening != 0):
+        raise ValueError(who + 'nesterov needs a momentum and zero '
+                         'dampening')
+    want = [('Y', Y, (M,)), ('steps', steps, (C,)), ('lr', lr, (C, T)),
+            ('replicas', replicas, (C, N)), ('mom_init', mom_init, (C,))]
+    if use_mom:
+        want.append(('in_mom', in_mom, (C, N)))
+    if snap.numel():
+        want.append(('snap', snap, (C, N)))
+    for name, t, shp in want:
+        if tuple(t.shape) != shp:
+            raise ValueError(who + '%s must be %s, got %s'
+                             % (name, list(shp), list(t.shape)))
+    if not 1 <= B <= CNNROUND_MAXB:
+        raise ValueError(who + 'unsupported B=%d (1 <= B <= %d)'
+                         % (B, CNNROUND_MAXB))
+    if k_cut < 0:
+        raise ValueError(who + 'k_cut is %d, expected >= 0' % k_cut)
+    if not 0 <= wd_numel <= N:
+        raise ValueError(who + 'wd_numel is %d, the arena has %d'
+                         % (wd_numel, N))
+    spans = cnn_layout_check(layout, X.shape[1], N)
+    n_steps = steps.tolist()
+    if max(n_steps) > T:
+        raise ValueError(who + 'steps holds %d but idx has T=%d'
+                         % (max(n_steps), T))
+    if int(idx.max()) >= M:
+        raise ValueError(who + 'idx holds row %d but X has %d rows'
+                         % (int(idx.max()), M))
+    for c in range(C):
+        for s in range(n_steps[c]):
+            if int((idx[c, s] >= 0).sum()) < 1:
+                raise ValueError(who + 'step %d of client %d has no sample'
+                                 % (s, c))
+    (Cin, S, _w1, _b1, C1, n1, _w2, _b2, C2, n2, _fw1, _fb1, H, _fw2, _fb2,
+     K) = _cnn_layout_flat(layout)
+    F2 = (spans[4][1] - spans[4][0]) // H
+    # (4-D shape as stored, nhwc) per tensor, in the order of `spans`
+    shapes = [((C1, Cin, 5, 5), n1), ((C1,), 0), ((C2, C1, 5, 5), n2),
+              ((C2,), 0), ((H, F2), 0), ((H,), 0), ((K, H), 0), ((K,), 0)]
+    loss = torch.zeros((C, T), dtype=torch.float32, device=dev)
+    inits = mom_init.tolist()
+    gap = torch.ones_like(server, dtype=torch.bool)
+    for lo, hi in spans:
+        gap[lo:hi] = False
+    for c in range(C):
+        if n_steps[c] <= 0:
+            continue
+        p = server.clone()
+        grad = torch.zeros_like(p)
+        mom_gaps = in_mom[c][gap].clone() if use_mom else None
+        for s in range(n_steps[c]):
+            if snap.numel() and s + 1 == k_cut:
+                snap[c].copy_(torch.where(gap, server, p))
+            rows = idx[c, s]
+            rows = rows[rows >= 0].long()
+            ts = []
+            for (lo, hi), (shp, nhwc) in zip(spans, shapes):
+                t = p[lo:hi].clone()
+                if nhwc:
+                    co, ci, kh, kw = shp
+                    t = t.view(co, kh, kw, ci).permute(0, 3, 1, 2)
+                else:
+                    t = t.view(shp)
+                ts.append(t.requires_grad_(True))
+            with torch.enable_grad():
+                a = X[rows].view(-1, Cin, S, S)
+                a = Fn.max_pool2d(Fn.relu(Fn.conv2d(a, ts[0], ts[1])), 2, 2)
+                a = Fn.max_pool2d(Fn.relu(Fn.conv2d(a, ts[2], ts[3])), 2, 2)
+                a = Fn.relu(Fn.linear(a.reshape(-1, F2), ts[4], ts[5]))
+                l = Fn.cross_entropy(Fn.linear(a, ts[6], ts[7]),
+                                     Y[rows].long())
+                gs = torch.autograd.grad(l, ts)
+            loss[c, s] = l.detach()
+            grad.zero_()
+            for (lo, hi), (_shp, nhwc), gt in zip(spans, shapes, gs):
+                if nhwc:
+                    gt = gt.permute(0, 2, 3, 1)
+                grad[lo:hi].copy_(gt.reshape(-1))
+            fused_sgd_step(
+                p, grad, lr=float(lr[c, s]), scale=1.0,
+                weight_decay=weight_decay, in_momentum=momentum,
+                out_momentum=0.0, dampening=dampening, nesterov=nesterov,
+                apply_lr=True, apply_in_momentum=use_mom,
+                apply_out_momentum=False,
+                in_buf=in_mom[c] if use_mom else None,
+                first_in=use_mom and not inits[c], wd_numel=wd_numel)
+            if use_mom:
+                inits[c] = 1
+        replicas[c].copy_(torch.where(gap, server, p))
+        if use_mom:
+            in_mom[c][gap] = mom_gaps
+            mom_init[c] = 1
+    return loss
+
+
+# --------------------------------------------------------------------------
 # small host-side math (not perf-critical)
 # --------------------------------------------------------------------------
 

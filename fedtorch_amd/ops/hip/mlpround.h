@@ -341,8 +341,10 @@ mlp_fwd_layer_k(const MlpRoundArgs a, int s, int li) {
 
 // head: logits, softmax cross-entropy, loss[c, s], dlogits / n.  One block
 // per client; the logits [B, K] are staged in LDS with row stride K | 1.
+// BIAS: the head has a bias at arena offset b_off (the CNN of cnnround.h).
+template <bool BIAS>
 __global__ void __launch_bounds__(MLPROUND_THREADS)
-mlp_head_k(const MlpRoundArgs a, int s) {
+mlp_head_k(const MlpRoundArgs a, int s, int b_off) {
   __shared__ float As[MLPROUND_MAXB * MLP_LD];
   __shared__ float Ws[MLP_TN * MLP_LD];
   __shared__ float Ls[MLPROUND_MAXB * (MLPROUND_MAXK + 1)];
@@ -369,8 +371,10 @@ mlp_head_k(const MlpRoundArgs a, int s) {
       __syncthreads();
     }
     if (j0 + tx < K) {
+      const float bias = BIAS ? W[b_off - a.lay.fc + j0 + tx] : 0.f;
 #pragma unroll
-      for (int m = 0; m < 8; ++m) Ls[(ty + 8 * m) * KS + j0 + tx] = acc[m];
+      for (int m = 0; m < 8; ++m)
+        Ls[(ty + 8 * m) * KS + j0 + tx] = BIAS ? acc[m] + bias : acc[m];
     }
   }
   __syncthreads();

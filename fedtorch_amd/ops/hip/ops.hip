@@ -22,6 +22,7 @@
 #include "gru.h"
 #include "linearround.h"
 #include "mlpround.h"
+#include "cnnround.h"
 
 #define CHK(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
 #define STREAM at::hip::getCurrentHIPStream().stream()
@@ -2820,7 +2821,8 @@ torch::Tensor mlp_local_rounds(
     for (int i = 1; i < (int)L; ++i)
       hipLaunchKernelGGL(mlp_fwd_layer_k<false>, dim3(Cu, tiles(lay.out[i])),
                          blk, 0, STREAM, a, s, i);
-    hipLaunchKernelGGL(mlp_head_k, dim3(Cu), blk, 0, STREAM, a, s);
+    hipLaunchKernelGGL(mlp_head_k<false>, dim3(Cu), blk, 0, STREAM, a, s,
+                       0);
     // without a correction: the kernels that know none
     for (int i = (int)L - 1; i >= 0; --i) {
       if (a.corr)
@@ -2844,7 +2846,224 @@ torch::Tensor mlp_local_rounds(
   return loss;
 }
 
+// ==========================================================================
+// packed CNN: all clients' local steps batched per layer (cnnround.h)
+// ==========================================================================
+// [max B, max K, max Cin, max S, max C1, max C2, max H]
+std::vector<int64_t> cnn_round_limits() {
+  return {CNNROUND_MAXB, CNNROUND_MAXK, CNNROUND_MAXCIN, CNNROUND_MAXS,
+          CNNROUND_MAXC1, CNNROUND_MAXC2, CNNROUND_MAXH};
+}
+
+// layout: [Cin, S, w1, b1, C1, nhwc1, w2, b2, C2, nhwc2, fw1, fb1, H, fw2,
+// fb2, K] -- the image, and arena offsets and shapes of conv1, conv2, fc1,
+// fc2.  Returns loss [C, T]; writes replicas / in_mom / mom_init / snap rows
+// of the clients with steps > 0.  idx and steps are range-checked on the host
+// unless the stream is capturing (the kernels never read X outside [0, M)).
+torch::Tensor cnn_local_rounds(
+    torch::Tensor X, torch::Tensor Y, torch::Tensor idx, torch::Tensor steps,
+    torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,
+    torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,
+    long k_cut, std::vector<int64_t> layout, long wd_numel,
+    double weight_decay, double momentum, double dampening, bool nesterov) {
+  const char* who = "cnn_local_rounds";
+  TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous(), who,
+              ": X must be contiguous [M, Cin*S*S] on GPU");
+  TORCH_CHECK(X.scalar_type() == torch::kFloat, who, ": X must be fp32");
+  const long M = X.size(0), F = X.size(1);
+  const auto dev = X.device();
+  TORCH_CHECK(M >= 1 && F >= 1, who, ": empty X");
+  TORCH_CHECK(M < (1L << 31), who, ": X too large");
+  TORCH_CHECK(server.dim() == 1 && server.size(0) < (1L << 30), who,
+              ": server must be [N], N < 2^30");
+  const long N = server.size(0);
+  linround_check(who, "Y", Y, torch::kInt, {M}, dev);
+  TORCH_CHECK(idx.dim() == 3, who, ": idx must be [C, T, B], got ",
+              idx.sizes());
+  const long C = idx.size(0), T = idx.size(1), B = idx.size(2);
+  TORCH_CHECK(C >= 1 && T >= 1, who, ": empty idx");
+  TORCH_CHECK(C < 65536 && T < (1L << 31), who, ": idx too large");
+  TORCH_CHECK(B >= 1 && B <= CNNROUND_MAXB, who, ": unsupported B=", B,
+              " (1 <= B <= ", CNNROUND_MAXB, ")");
+  linround_check(who, "idx", idx, torch::kInt, {C, T, B}, dev);
+  linround_check(who, "steps", steps, torch::kInt, {C}, dev);
+  linround_check(who, "lr", lr, torch::kFloat, {C, T}, dev);
+  linround_check(who, "server", server, torch::kFloat, {N}, dev);
+  linround_check(who, "replicas", replicas, torch::kFloat, {C, N}, dev);
+  linround_check(who, "mom_init", mom_init, torch::kInt, {C}, dev);
+  const bool use_mom = momentum != 0.0;
+  if (use_mom)
+    linround_check(who, "in_mom", in_mom, torch::kFloat, {C, N}, dev);
+  const bool has_snap = snap.numel() != 0;
+  if (has_snap) linround_check(who, "snap", snap, torch::kFloat, {C, N}, dev);
+  TORCH_CHECK(k_cut >= 0, who, ": k_cut is ", k_cut, ", expected >= 0");
+  TORCH_CHECK(!nesterov || (use_mom && dampening == 0.0), who,
+              ": nesterov needs a momentum and zero dampening");
+  TORCH_CHECK(wd_numel >= 0 && wd_numel <= N, who, ": wd_numel is ", wd_numel,
+              ", the arena has ", N);
+
+  // the layout
+  TORCH_CHECK(layout.size() == 16, who, ": layout must hold 16 numbers "
+              "(image, conv1, conv2, fc1, fc2), got ", layout.size());
+  const long Cin = layout[0], S = layout[1], C1 = layout[4], C2 = layout[8],
+             H = layout[12], K = layout[15];
+  TORCH_CHECK(Cin >= 1 && Cin <= CNNROUND_MAXCIN && S >= 1 &&
+                  S <= CNNROUND_MAXS,
+              who, ": unsupported image (Cin=", Cin, ", S=", S,
+              "), 1 <= Cin <= ", CNNROUND_MAXCIN, ", S <= ", CNNROUND_MAXS);
+  TORCH_CHECK(S >= 6 && (S - 4) % 2 == 0 && (S - 4) / 2 >= 6 &&
+                  ((S - 4) / 2 - 4) % 2 == 0,
+              who, ": S=", S, " does not pool evenly twice (S - 4 and "
+              "(S - 4) / 2 - 4 even, the last map at least 1x1)");
+  const long S1 = (S - 4) / 2, O2 = S1 - 4, S2 = O2 / 2, F2 = C2 * S2 * S2;
+  TORCH_CHECK(F == Cin * S * S, who, ": X has ", F, " features, the image (",
+              Cin, ", ", S, ", ", S, ") has ", Cin * S * S);
+  TORCH_CHECK(C1 >= 1 && C1 <= CNNROUND_MAXC1 && C2 >= 1 &&
+                  C2 <= CNNROUND_MAXC2 && H >= 1 && H <= CNNROUND_MAXH,
+              who, ": unsupported C1=", C1, " C2=", C2, " H=", H,
+              " (C1 <= ", CNNROUND_MAXC1, ", C2 <= ", CNNROUND_MAXC2,
+              ", H <= ", CNNROUND_MAXH, ")");
+  TORCH_CHECK(K >= 1 && K <= CNNROUND_MAXK, who, ": unsupported K=", K,
+              " (1 <= K <= ", CNNROUND_MAXK, ")");
+  for (int i : {5, 9})
+    TORCH_CHECK(layout[i] == 0 || layout[i] == 1, who,
+                ": the nhwc flag of a conv must be 0 or 1, got ", layout[i]);
+  std::vector<std::pair<long, long>> spans;      // [start, end) in the arena
+  auto span = [&](long off, long len, const char* what) {
+    TORCH_CHECK(off >= 0 && off + len <= N, who, ": layout ", what, " [", off,
+                ", +", len, ") does not fit the arena of ", N);
+    spans.emplace_back(off, off + len);
+  };
+  span(layout[2], C1 * Cin * 25, "conv1 weight");
+  span(layout[3], C1, "conv1 bias");
+  span(layout[6], C2 * C1 * 25, "conv2 weight");
+  span(layout[7], C2, "conv2 bias");
+  span(layout[10], H * F2, "fc1 weight");
+  span(layout[11], H, "fc1 bias");
+  span(layout[13], K * H, "fc2 weight");
+  span(layout[14], K, "fc2 bias");
+  std::sort(spans.begin(), spans.end());
+  for (size_t i = 1; i < spans.size(); ++i)
+    TORCH_CHECK(spans[i - 1].second <= spans[i].first, who,
+                ": layout tensors overlap at arena element ", spans[i].first);
+
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(STREAM, &cap) == hipSuccess, who,
+              ": hipStreamIsCapturing failed");
+  if (cap == hipStreamCaptureStatusNone) {
+    const long top = idx.max().item<int>();
+    TORCH_CHECK(top < M, who, ": idx holds row ", top, " but X has ", M,
+                " rows");
+    const long most = steps.max().item<int>();
+    TORCH_CHECK(most <= T, who, ": steps holds ", most, " but idx has T=", T);
+  }
+
+  CnnLayout lay;
+  lay.Cin = (int)Cin; lay.S = (int)S; lay.C1 = (int)C1; lay.C2 = (int)C2;
+  lay.H = (int)H; lay.K = (int)K;
+  lay.S1 = (int)S1; lay.S2 = (int)S2; lay.O2 = (int)O2; lay.F2 = (int)F2;
+  lay.w1 = (int)layout[2]; lay.b1 = (int)layout[3];
+  lay.nhwc1 = (int)layout[5];
+  lay.w2 = (int)layout[6]; lay.b2 = (int)layout[7];
+  lay.nhwc2 = (int)layout[9];
+  lay.fw1 = (int)layout[10]; lay.fb1 = (int)layout[11];
+  lay.fw2 = (int)layout[13]; lay.fb2 = (int)layout[14];
+  // workspace per client: p1, p2, a, dlogits, dz1, dp2, dp1; argmax bytes
+  const long np1 = C1 * S1 * S1;
+  long off = 0;
+  lay.p1 = (int)off;  off += B * np1;
+  lay.p2 = (int)off;  off += B * F2;
+  lay.act = (int)off; off += B * H;
+  lay.dl = (int)off;  off += B * K;
+  lay.dz1 = (int)off; off += B * H;
+  lay.dp2 = (int)off; off += B * F2;
+  lay.dp1 = (int)off; off += B * np1;
+  lay.am1 = 0;
+  lay.am2 = (int)(B * np1);
+  lay.wsb_stride = B * np1 + B * F2;
+  auto ws = torch::empty({C, off}, X.options());
+  auto wsb = torch::empty({C, lay.wsb_stride},
+                          X.options().dtype(torch::kUInt8));
+  auto loss = torch::zeros({C, T}, X.options());
+
+  CnnRoundArgs a;
+  MlpRoundArgs& m = a.m;
+  m.X = X.data_ptr<float>();
+  m.Y = Y.data_ptr<int>();
+  m.idx = idx.data_ptr<int>();
+  m.steps = steps.data_ptr<int>();
+  m.lr = lr.data_ptr<float>();
+  m.server = server.data_ptr<float>();
+  m.replicas = replicas.data_ptr<float>();
+  m.in_mom = use_mom ? in_mom.data_ptr<float>() : nullptr;
+  m.mom_init = mom_init.data_ptr<int>();
+  m.snap = has_snap ? snap.data_ptr<float>() : nullptr;
+  m.loss = loss.data_ptr<float>();
+  m.ws = ws.data_ptr<float>();
+  m.corr_rows = nullptr; m.ctrl_s = nullptr;
+  m.M = (int)M; m.B = (int)B; m.T = (int)T; m.N = (int)N;
+  m.k_cut = (int)std::min<long>(k_cut, 1L << 30);
+  m.use_mom = use_mom; m.nesterov = nesterov; m.wd_numel = (int)wd_numel;
+  m.wd = (float)weight_decay; m.mom = (float)momentum;
+  m.omd = (float)(1.0 - dampening); m.eps = 0.f;
+  m.prox_mu = 0.f; m.corr = 0;
+  // what mlp_head_k reads: one block whose activation is fc1's
+  m.lay = MlpLayout{};
+  m.lay.L = 1;
+  m.lay.act[0] = lay.act; m.lay.dz[1] = lay.dl;
+  m.lay.fc = lay.fw2; m.lay.H = lay.H; m.lay.K = lay.K;
+  m.lay.ws_stride = off;
+  a.lay = lay;
+  a.wsb = wsb.data_ptr<uint8_t>();
+
+  const dim3 blk(CNNROUND_THREADS);
+  auto tiles = [](long n) { return (unsigned)((n + MLP_TN - 1) / MLP_TN); };
+  const unsigned rowb =
+      (unsigned)std::min<long>((N + 4 * MLPROUND_THREADS - 1) /
+                                   (4 * MLPROUND_THREADS), 64);
+  const unsigned Cu = (unsigned)C, Bu = (unsigned)B;
+  const long K2 = 25 * C1, Kp = (K2 + 3) / 4 * 4, npx = O2 * O2;
+  const size_t lds_fwd = sizeof(float) * (Kp * 16 + np1 + Kp);
+  const size_t lds_dg = sizeof(float) *
+      (CNN_DG_CO * (S1 + 4) * (S1 + 4) + 25 * CNN_DG_CO * 17);
+  const size_t lds_wrw = sizeof(float) *
+      (CNNROUND_MAXC2 * (npx | 1) + np1 + 16 * CNN_WRW_NT + npx +
+       CNNROUND_THREADS);
+  const unsigned t16c2 = (unsigned)((C2 + 15) / 16);
+  const unsigned t16c1 = (unsigned)((C1 + 15) / 16);
+  const unsigned nwrw =
+      (unsigned)((K2 + 16 * CNN_WRW_NT - 1) / (16 * CNN_WRW_NT));
+  hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, rowb), blk, 0, STREAM, m, 0);
+  for (int s = 0; s < (int)T; ++s) {
+    if (has_snap && s + 1 == k_cut)
+      hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, rowb), blk, 0, STREAM, m, 1);
+    hipLaunchKernelGGL(cnn_conv1_fwd_k, dim3(Cu, Bu), blk, 0, STREAM, a, s);
+    hipLaunchKernelGGL(cnn_conv2_fwd_k,
+                       dim3(Cu, t16c2, std::min(Bu, 8u)), blk, lds_fwd,
+                       STREAM, a, s);
+    hipLaunchKernelGGL(cnn_fc1_fwd_k, dim3(Cu, tiles(H)), blk, 0, STREAM, a,
+                       s);
+    hipLaunchKernelGGL(mlp_head_k<true>, dim3(Cu), blk, 0, STREAM, m, s,
+                       lay.fb2);
+    hipLaunchKernelGGL(cnn_fc_bwd_k<true>, dim3(Cu, tiles(H)), blk, 0, STREAM,
+                       a, s);
+    hipLaunchKernelGGL(cnn_fc_bwd_k<false>, dim3(Cu, tiles(F2)), blk, 0,
+                       STREAM, a, s);
+    hipLaunchKernelGGL(cnn_conv2_dgrad_k, dim3(Cu, t16c1, Bu), blk, lds_dg,
+                       STREAM, a, s);
+    hipLaunchKernelGGL(cnn_conv2_wrw_k, dim3(Cu, nwrw), blk, lds_wrw, STREAM,
+                       a, s);
+    hipLaunchKernelGGL(cnn_conv1_wrw_k, dim3(Cu, (unsigned)C1), blk, 0,
+                       STREAM, a, s);
+  }
+  if (use_mom)
+    hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, 1), blk, 0, STREAM, m, 2);
+  return loss;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("cnn_local_rounds", &cnn_local_rounds);
+  m.def("cnn_round_limits", &cnn_round_limits);
   m.def("mlp_local_rounds", &mlp_local_rounds);
   m.def("mlp_round_max_batch", &mlp_round_max_batch);
   m.def("mlp_round_max_classes", &mlp_round_max_classes);

@@ -49,6 +49,14 @@ _BATCHED_MLP_CORR_ENABLED = \
 PACKED_TYPES = ('fedavg', 'fedprox', 'scaffold', 'fedgate')
 
 
+# Packed CNN clients (the LeNet-style `cnn`): the local steps of all online
+# clients batched per layer (ops.cnn_local_rounds, hip/cnnround.h).  Its own
+# opt-in: ``FEDTORCH_PACKED_BATCHED_CNN=1``; timings in
+# profiles/packed_cnn_notes.md.
+_BATCHED_CNN_ENABLED = \
+    os.environ.get('FEDTORCH_PACKED_BATCHED_CNN', '0') == '1'
+
+
 class VirtualGraph(object):
     """graph facade so the dataset pipeline partitions over W*C clients."""
 
@@ -180,21 +188,9 @@ class ClientPack(object):
         if layout is None:
             why.append('model is not a plain logistic regression / least '
                        'squares')
-        if getattr(client.arena, 'half_flat', None) is not None \
-                or getattr(args, 'bf16', False):
-            why.append('bf16 compute')
-        if not self._batched_type_ok(_BATCHED_CORR_ENABLED):
-            why.append('federated_type is not fedavg')
+        why += self._run_blockers(
+            self._batched_type_ok(_BATCHED_CORR_ENABLED))
         opt = client.optimizer
-        if getattr(opt, '_prox_mu', 0.0) != 0.0 or any(
-                getattr(opt, a, None) is not None
-                for a in ('_server', '_ctrl_server', '_ctrl_client',
-                          '_delta')):
-            why.append('a gradient correction is bound on the optimizer')
-        if getattr(args, 'federated_sync_type', None) != 'local_step':
-            why.append('federated_sync_type is not local_step')
-        if getattr(args, 'growing_batch_size', False):
-            why.append('growing_batch_size')
         loaders = self.train_loaders
         if not all(isinstance(l, DeviceCachedLoader) and not l._aug
                    for l in loaders):
@@ -230,6 +226,53 @@ class ClientPack(object):
 
     def batched_eligible(self):
         return not self.batched_blockers()
+
+    def _run_blockers(self, type_ok):
+        """What every batched path refuses about the run: bf16, a federated
+        type the path does not take (`type_ok`), a correction bound on the
+        optimizer, the sync type, a growing batch size."""
+        args, opt = self.args, self.base.optimizer
+        why = []
+        if getattr(self.base.arena, 'half_flat', None) is not None \
+                or getattr(args, 'bf16', False):
+            why.append('bf16 compute')
+        if not type_ok:
+            why.append('federated_type is not fedavg')
+        if getattr(opt, '_prox_mu', 0.0) != 0.0 or any(
+                getattr(opt, a, None) is not None
+                for a in ('_server', '_ctrl_server', '_ctrl_client',
+                          '_delta')):
+            why.append('a gradient correction is bound on the optimizer')
+        if getattr(args, 'federated_sync_type', None) != 'local_step':
+            why.append('federated_sync_type is not local_step')
+        if getattr(args, 'growing_batch_size', False):
+            why.append('growing_batch_size')
+        return why
+
+    def _class_loader_blockers(self, min_b, max_b):
+        """What the layer-batched classifier paths (MLP, CNN) refuse about
+        the loaders: (reasons, whether every loader is an un-augmented
+        DeviceCachedLoader -- only then can its rows be looked at)."""
+        from fedtorch_amd.components.datasets.device_cache import \
+            DeviceCachedLoader
+        loaders = self.train_loaders
+        if not all(isinstance(l, DeviceCachedLoader) and not l._aug
+                   for l in loaders):
+            return ['a local loader is not an un-augmented '
+                    'DeviceCachedLoader'], False
+        why = []
+        B = loaders[0].batch_size
+        if any(l.batch_size != B for l in loaders):
+            why.append('batch sizes differ between clients')
+        elif not min_b <= B <= max_b:
+            why.append('batch size %d outside %d .. %d' % (B, min_b, max_b))
+        # the slot loop's `break` on a 1-sample batch is not reproduced
+        if any(not l.drop_last and len(l.x) % l.batch_size == 1
+               for l in loaders):
+            why.append('a partition leaves a 1-sample last batch')
+        if any(l.y.is_floating_point() for l in loaders):
+            why.append('class labels are not integers')
+        return why, True
 
     def _batched_type_ok(self, corr_enabled):
         """fedavg always; fedprox / scaffold / dense fedgate when the path's
@@ -303,9 +346,6 @@ class ClientPack(object):
     def mlp_batched_blockers(self):
         """Why this pack's rounds cannot run through ops.mlp_local_rounds: a
         list of reasons, empty when they can."""
-        from fedtorch_amd.components.datasets.device_cache import \
-            DeviceCachedLoader
-        args, client = self.args, self.base
         why = []
         if not _BATCHED_MLP_ENABLED:
             why.append('FEDTORCH_PACKED_BATCHED_MLP is not set')
@@ -316,53 +356,95 @@ class ClientPack(object):
                        'arena')
         elif self.mlp_eps() is None:
             why.append('BatchNorm layers differ in eps')
-        if getattr(client.arena, 'half_flat', None) is not None \
-                or getattr(args, 'bf16', False):
-            why.append('bf16 compute')
-        if not self._batched_type_ok(_BATCHED_MLP_CORR_ENABLED):
-            why.append('federated_type is not fedavg')
-        opt = client.optimizer
-        if getattr(opt, '_prox_mu', 0.0) != 0.0 or any(
-                getattr(opt, a, None) is not None
-                for a in ('_server', '_ctrl_server', '_ctrl_client',
-                          '_delta')):
-            why.append('a gradient correction is bound on the optimizer')
-        if getattr(args, 'federated_sync_type', None) != 'local_step':
-            why.append('federated_sync_type is not local_step')
-        if getattr(args, 'growing_batch_size', False):
-            why.append('growing_batch_size')
-        loaders = self.train_loaders
-        if not all(isinstance(l, DeviceCachedLoader) and not l._aug
-                   for l in loaders):
-            why.append('a local loader is not an un-augmented '
-                       'DeviceCachedLoader')
-        else:
-            B = loaders[0].batch_size
-            if any(l.batch_size != B for l in loaders):
-                why.append('batch sizes differ between clients')
-            elif not 2 <= B <= ops.MLPROUND_MAXB:
-                why.append('batch size %d outside 2 .. %d'
-                           % (B, ops.MLPROUND_MAXB))
-            # the slot loop's `break` on a 1-sample batch is not reproduced
-            if any(not l.drop_last and len(l.x) % l.batch_size == 1
-                   for l in loaders):
-                why.append('a partition leaves a 1-sample last batch')
-            if any(l.y.is_floating_point() for l in loaders):
-                why.append('class labels are not integers')
-            if layout is not None:
-                F = layout['blocks'][0][4]
-                if any(l.x[0].numel() != F for l in loaders):
-                    why.append('loader rows do not have %d features' % F)
-                if layout['head'][2] > ops.MLPROUND_MAXK:
-                    why.append('K=%d classes (K <= %d)'
-                               % (layout['head'][2], ops.MLPROUND_MAXK))
-                if len(layout['blocks']) > ops.MLPROUND_MAXL:
-                    why.append('%d blocks (L <= %d)'
-                               % (len(layout['blocks']), ops.MLPROUND_MAXL))
+        why += self._run_blockers(
+            self._batched_type_ok(_BATCHED_MLP_CORR_ENABLED))
+        reasons, cached = self._class_loader_blockers(2, ops.MLPROUND_MAXB)
+        why += reasons
+        if cached and layout is not None:
+            F = layout['blocks'][0][4]
+            if any(l.x[0].numel() != F for l in self.train_loaders):
+                why.append('loader rows do not have %d features' % F)
+            if layout['head'][2] > ops.MLPROUND_MAXK:
+                why.append('K=%d classes (K <= %d)'
+                           % (layout['head'][2], ops.MLPROUND_MAXK))
+            if len(layout['blocks']) > ops.MLPROUND_MAXL:
+                why.append('%d blocks (L <= %d)'
+                           % (len(layout['blocks']), ops.MLPROUND_MAXL))
         return why
 
     def mlp_batched_eligible(self):
         return not self.mlp_batched_blockers()
+
+    # ---- batched round of a CNN (trainings/packed.py) ----------------------
+    def cnn_layout(self):
+        """The layout ops.cnn_local_rounds takes -- dict(image=(Cin, S),
+        conv1 / conv2=(w_off, b_off, C, nhwc), fc1 / fc2=(w_off, b_off, out))
+        -- of the compute module in the arena, or None when the module is
+        not exactly the LeNet-style CNN whose eight parameters are exactly
+        the arena's.  `nhwc`: the arena packs that conv weight in
+        channels_last element order (`Arena.cl`)."""
+        from fedtorch_amd.components.models.cnn import CNN
+        model, arena = self.base.model, self.base.arena
+        if type(model) is not CNN:
+            return None
+        names = ['%s.%s' % (m, w) for m in ('conv1', 'conv2', 'fc1', 'fc2')
+                 for w in ('weight', 'bias')]
+        if sorted(arena.names) != sorted(names):
+            return None
+        for conv in (model.conv1, model.conv2):
+            if conv.kernel_size != (5, 5) or conv.stride != (1, 1) \
+                    or conv.padding != (0, 0) or conv.dilation != (1, 1) \
+                    or conv.groups != 1:
+                return None
+        if model.conv2.in_channels != model.conv1.out_channels \
+                or model.fc2.in_features != model.fc1.out_features:
+            return None
+        Cin, C1, C2 = (model.conv1.in_channels, model.conv1.out_channels,
+                       model.conv2.out_channels)
+        # the image side from fc1's features C2 * S2^2: S = 4 S2 + 12
+        S2 = int(round((model.fc1.in_features / float(C2)) ** .5))
+        if C2 * S2 * S2 != model.fc1.in_features or S2 < 1:
+            return None
+        at = lambda n: arena.names.index(n)  # noqa: E731
+        off = lambda n: arena.offsets[at(n)]  # noqa: E731
+        return dict(
+            image=(int(Cin), 4 * S2 + 12),
+            conv1=(off('conv1.weight'), off('conv1.bias'), int(C1),
+                   int(bool(arena.cl[at('conv1.weight')]))),
+            conv2=(off('conv2.weight'), off('conv2.bias'), int(C2),
+                   int(bool(arena.cl[at('conv2.weight')]))),
+            fc1=(off('fc1.weight'), off('fc1.bias'),
+                 int(model.fc1.out_features)),
+            fc2=(off('fc2.weight'), off('fc2.bias'),
+                 int(model.fc2.out_features)))
+
+    def cnn_batched_blockers(self):
+        """Why this pack's rounds cannot run through ops.cnn_local_rounds: a
+        list of reasons, empty when they can."""
+        why = []
+        if not _BATCHED_CNN_ENABLED:
+            why.append('FEDTORCH_PACKED_BATCHED_CNN is not set')
+        layout = self.cnn_layout()
+        if layout is None:
+            why.append('model is not the LeNet-style CNN (5x5 convs, 2x2 '
+                       'pools, two Linear layers) that fills the arena')
+        why += self._run_blockers(
+            getattr(self.args, 'federated_type', None) == 'fedavg')
+        reasons, cached = self._class_loader_blockers(1, ops.CNNROUND_MAXB)
+        why += reasons
+        if cached and layout is not None:
+            Cin, S = layout['image']
+            F = Cin * S * S
+            if any(l.x[0].numel() != F for l in self.train_loaders):
+                why.append('loader rows do not have %d features' % F)
+            try:
+                ops.cnn_layout_check(layout, F, self.base.arena.numel)
+            except ValueError as e:
+                why.append(str(e))
+        return why
+
+    def cnn_batched_eligible(self):
+        return not self.cnn_batched_blockers()
 
     def stacked_data(self):
         """(X [M, F] fp32, Y [M] int32 labels | fp32 targets, offsets [C+1]):

@@ -141,13 +141,16 @@ def _plan_local_rounds(client, pack, online):
 
 
 def _batched_local_rounds(client, pack, server, online, snap, k_cut,
-                          mlp=False):
+                          mlp=False, cnn=False):
     """The local steps of ALL online local clients in one batched op call:
     ops.linear_local_rounds for a linear model (FEDTORCH_PACKED_BATCHED,
     `ClientPack.batched_eligible`), ops.mlp_local_rounds for an MLP
     (`mlp=True`: FEDTORCH_PACKED_BATCHED_MLP,
     `ClientPack.mlp_batched_eligible`), either with the gradient correction
-    of the federated type (`ClientPack.batched_correction`).
+    of the federated type (`ClientPack.batched_correction`);
+    ops.cnn_local_rounds for the LeNet-style CNN (`cnn=True`:
+    FEDTORCH_PACKED_BATCHED_CNN, `ClientPack.cnn_batched_eligible`, FedAvg
+    only).
 
     The host first walks the counters (`_plan_local_rounds`).  `snap`:
     DRFA's [C, N] snapshot arena, row j receives client j's parameters before
@@ -167,7 +170,11 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
     sgd = dict(weight_decay=g['weight_decay'], momentum=momentum,
                dampening=g['dampening'], nesterov=g['nesterov'])
     corr = pack.batched_correction()
-    if mlp:
+    if cnn:
+        loss = ops.cnn_local_rounds(
+            *operands, layout=pack.cnn_layout(),
+            wd_numel=client.arena.wd_numel, **sgd)
+    elif mlp:
         loss = ops.mlp_local_rounds(
             *operands, layout=pack.mlp_layout(), eps=pack.mlp_eps(),
             wd_numel=client.arena.wd_numel, **sgd, **corr)
@@ -228,12 +235,17 @@ def train_and_validate_federated_packed(client, pack, validate=False):
     # MLP: the clients' steps batched per layer (off unless
     # FEDTORCH_PACKED_BATCHED_MLP=1 and the pack qualifies)
     batched_mlp = not batched and pack.mlp_batched_eligible()
+    # CNN: likewise (off unless FEDTORCH_PACKED_BATCHED_CNN=1 and the pack
+    # qualifies)
+    batched_cnn = not batched and not batched_mlp \
+        and pack.cnn_batched_eligible()
     log('packed local steps: {}'.format(
         'one batched launch per round' if batched
         else 'MLP layers batched over the clients' if batched_mlp
+        else 'CNN layers batched over the clients' if batched_cnn
         else 'slot loop'),
         args.debug)
-    batched = batched or batched_mlp
+    batched = batched or batched_mlp or batched_cnn
     run_client = (lambda j, server_flat, fn: None) if batched \
         else pack.run_client
     if ftype == 'scaffold':
@@ -312,7 +324,7 @@ def train_and_validate_federated_packed(client, pack, validate=False):
         if batched:
             _loss, taus, lrs = _batched_local_rounds(
                 client, pack, server, online, kth if drfa else None,
-                k_cut if drfa else 0, mlp=batched_mlp)
+                k_cut if drfa else 0, mlp=batched_mlp, cnn=batched_cnn)
 
         partial = pack.accumulate_partial(server, weights)
         if ftype == 'scaffold':
