@@ -776,7 +776,9 @@ def cnn_layout_check(layout, F, N):
 
 def cnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
                      mom_init, snap, k_cut, *, layout, wd_numel,
-                     weight_decay, momentum, dampening, nesterov):
+                     weight_decay, momentum, dampening, nesterov,
+                     delta=None, ctrl_server=None, ctrl_client=None,
+                     prox_mu=0.0):
     """All local SGD steps of a round, for every packed client of the
     LeNet-style CNN of `components/models/cnn.py`, batched per layer.
 
@@ -806,13 +808,19 @@ def cnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
         a  = relu(flat(p2) Wf1^T + bf1)            flat (c2 * S2 + h) * S2 + w
         logits = a Wf2^T + bf2 ; loss[c, s] = mean CE(logits, Y[r])
         backward of exactly that (pool: the first maximum of a window in
-        scan order; ReLU mask z > 0) ; d = grad ; d += wd p for arena index
+        scan order; ReLU mask z > 0) ; d = grad ; [delta] d -= delta[c] ;
+        [control pair] d += ctrl_server - ctrl_client[c] ;
+        [prox_mu] d += prox_mu (p - server) ; d += wd p for arena index
         < wd_numel ; momentum / dampening / nesterov / first use
         (mom_init[c] == 0 at s == 0: buf = d) ; p -= lr[c, s] d
-        -- the local branch of `fused_sgd_step`, in place in replicas[c]
-        (and in_mom[c])
+        -- the local branch of `fused_sgd_step` with its gradient
+        corrections, in place in replicas[c] (and in_mom[c])
       mom_init[c] <- 1 (with momentum)
 
+    delta [C, N], or the pair ctrl_server [N] / ctrl_client [C, N], and
+    prox_mu >= 0 are constant over the call; only the parameter elements of
+    the correction rows of clients with steps > 0 are read.  A call without
+    a correction runs the kernels that know none.
     Pad gaps of in_mom stay as they were; in_mom / mom_init are touched only
     when momentum != 0.  Returns loss [C, T]: the mean loss of each executed
     step, 0 elsewhere.  The eager twin raises ValueError for an executed
@@ -828,14 +836,17 @@ def cnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
             X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap,
             int(k_cut), _cnn_layout_flat(layout), int(wd_numel),
             float(weight_decay), float(momentum), float(dampening),
-            bool(nesterov))
+            bool(nesterov),
+            *(t if t is not None else torch.empty(0, device=dev)
+              for t in (delta, ctrl_server, ctrl_client)), float(prox_mu))
 
     # eager twin: a per-client, per-step loop; the gradients come from
     # autograd over F.conv2d / F.max_pool2d / F.relu / F.linear /
     # F.cross_entropy, the update from the fused-SGD twin above over the
     # whole row -- the ops of the packed slot loop, in its order.  Pad gaps
     # (zero in a real arena, where the whole-row update leaves them zero) are
-    # put back afterwards.
+    # put back afterwards; those of the correction rows are masked, never
+    # used.
     import torch.nn.functional as Fn
     who = 'cnn_local_rounds: '
     for name, t, dt in (('X', X, torch.float32), ('Y', Y, torch.int32),
@@ -869,6 +880,24 @@ def cnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
         want.append(('in_mom', in_mom, (C, N)))
     if snap.numel():
         want.append(('snap', snap, (C, N)))
+    if (ctrl_server is None) != (ctrl_client is None):
+        raise ValueError(who + 'ctrl_server and ctrl_client come as a pair')
+    if delta is not None and ctrl_server is not None:
+        raise ValueError(who + 'delta and a control pair together are not '
+                         'supported (one correction vector per client)')
+    for name, t, shp in (('delta', delta, (C, N)),
+                         ('ctrl_server', ctrl_server, (N,)),
+                         ('ctrl_client', ctrl_client, (C, N))):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() \
+                or t.device != dev:
+            raise ValueError(who + '%s must be contiguous %s on %s'
+                             % (name, torch.float32, dev))
+        want.append((name, t, shp))
+    if not (0 <= prox_mu < float('inf')):
+        raise ValueError(who + 'prox_mu must be finite and >= 0, got %r'
+                         % (prox_mu,))
     for name, t, shp in want:
         if tuple(t.shape) != shp:
             raise ValueError(who + '%s must be %s, got %s'
@@ -905,11 +934,21 @@ def cnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
     gap = torch.ones_like(server, dtype=torch.bool)
     for lo, hi in spans:
         gap[lo:hi] = False
+    zero = torch.zeros_like(server)
+    live = lambda t: torch.where(gap, zero, t)  # noqa: E731
     for c in range(C):
         if n_steps[c] <= 0:
             continue
         p = server.clone()
         grad = torch.zeros_like(p)
+        corr = {}
+        if prox_mu != 0:
+            corr.update(prox_mu=prox_mu, server=server)
+        if delta is not None:
+            corr['delta'] = live(delta[c])
+        if ctrl_server is not None:
+            corr.update(ctrl_server=live(ctrl_server),
+                        ctrl_client=live(ctrl_client[c]))
         mom_gaps = in_mom[c][gap].clone() if use_mom else None
         for s in range(n_steps[c]):
             if snap.numel() and s + 1 == k_cut:
@@ -946,7 +985,8 @@ def cnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
                 apply_lr=True, apply_in_momentum=use_mom,
                 apply_out_momentum=False,
                 in_buf=in_mom[c] if use_mom else None,
-                first_in=use_mom and not inits[c], wd_numel=wd_numel)
+                first_in=use_mom and not inits[c], wd_numel=wd_numel,
+                **corr)
             if use_mom:
                 inits[c] = 1
         replicas[c].copy_(torch.where(gap, server, p))

@@ -2,7 +2,8 @@
 // kernel's grid has a client dimension, the weights are read from (and
 // updated in) the [C, N] replica arena -- the scheme of mlpround.h, whose
 // round-begin / snapshot kernel (mlp_rows_k), row helper, 32x32 tiles, head
-// kernel and SGD update (mlp_sgd / mlp_update<false>) are used as they are.
+// kernel, SGD update and gradient correction (mlp_sgd / mlp_corr_load /
+// mlp_update) are used as they are.
 //
 // The model (components/models/cnn.py): conv 5x5 / stride 1 / no padding +
 // bias, ReLU, max-pool 2/2, twice; then fc1 + ReLU and fc2, mean softmax
@@ -22,6 +23,9 @@
 //       dp1 = dgrad(dz2, W2), dz2 = dp2 through the argmax   cnn_conv2_dgrad_k
 //       dW2 = wrw(dz2, p1), db2 ; SGD on W2, b2              cnn_conv2_wrw_k
 //       dW1 = wrw(dz1c, x), db1 ; SGD on W1, b1              cnn_conv1_wrw_k
+//       every SGD update with fused_sgd_step's gradient corrections:
+//         d = g ; [delta] d -= delta[c] ; [control pair] d += c - c_c[c] ;
+//         [prox_mu] d += mu (p - server) ; then wd, momentum, p -= lr d
 //     mom_init[c] <- 1 (with momentum)                       mlp_rows_k(2)
 //
 // 9 launches per step, 256 threads each.  Every kernel takes the step s and
@@ -63,6 +67,18 @@
 // >= M) are never dereferenced, their workspace rows are never read, and
 // they are excluded from n.  Only parameter elements of the rows of online
 // clients are written (replicas: the whole row first).
+//
+// A gradient correction is constant over the round and indexed by the arena
+// element e that addresses the parameter, whatever the order of a conv
+// weight.  The three kernels that update parameters exist twice (template
+// <bool CORR>): without a correction the launcher runs code that knows none.
+// With one, each update site issues its correction loads ahead of the sums
+// that precede the update (cnn_conv2_wrw_k: in the epilogue, the four of a
+// 16-column tile ahead of that tile's updates, so that the MFMA loop keeps
+// its registers and occupancy); lanes run along e at every site, so the
+// loads coalesce like the momentum's.  Only parameter
+// elements of the correction rows of clients with steps > 0 are read, and
+// none past the client's last step.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.h"
@@ -297,7 +313,8 @@ cnn_fc1_fwd_k(const CnnRoundArgs a, int s) {
 //         dz1 = da [a > 0] ; SGD on bf1[tile] ; block 0: SGD on bf2.
 //   !TOP  fc1 | p2:  M = Wf1 [H, F2]; dp2 = dz1 M ; SGD on M[:, tile].
 // The block owns the column slab of M, so dgrad sees pre-update weights.
-template <bool TOP>
+// CORR: the SGD updates take the round's gradient correction.
+template <bool TOP, bool CORR>
 __global__ void __launch_bounds__(CNNROUND_THREADS)
 cnn_fc_bwd_k(const CnnRoundArgs a, int s) {
   __shared__ float As[MLPROUND_MAXB * MLP_LD];   // dz_M chunk, later dz1
@@ -310,8 +327,7 @@ cnn_fc_bwd_k(const CnnRoundArgs a, int s) {
   const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
   const int j0 = blockIdx.y * MLP_TN;
   mlp_rows(a.m, c, s, rid);
-  const MlpSgd u = mlp_sgd<false>(a.m, c, s);
-  const MlpCorr k0 = {0.f, 0.f};
+  const MlpSgd u = mlp_sgd<CORR>(a.m, c, s);
   float* ws = a.m.ws + (long)c * a.m.lay.ws_stride;
   const int ncol = TOP ? L.H : L.F2, nO = TOP ? L.K : L.H;
   const int m_off = TOP ? L.fw2 : L.fw1;
@@ -326,6 +342,16 @@ cnn_fc_bwd_k(const CnnRoundArgs a, int s) {
   for (int o0 = 0; o0 < nO; o0 += MLP_TN) {
     mlp_load_a<false>(As, dzM, nO, o0, nO, rid);
     mlp_load_w<true>(Ws, u.p + m_off, j0, ncol, o0, nO);
+    // the correction of the chunk's elements: issued here, used after the
+    // rows
+    MlpCorr kc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int oo = ty + 8 * q;
+      kc[q] = MlpCorr{0.f, 0.f};
+      if (cin && o0 + oo < nO)
+        kc[q] = mlp_corr_load<CORR>(u, m_off + (o0 + oo) * ncol + col);
+    }
     __syncthreads();
     mlp_fma_tile(acc, As, Ws);
     // weight gradient of M[o0 + oo][col], oo = ty + 8 q, rows in order
@@ -340,8 +366,8 @@ cnn_fc_bwd_k(const CnnRoundArgs a, int s) {
     for (int q = 0; q < 4; ++q) {
       const int oo = ty + 8 * q;
       if (cin && o0 + oo < nO)
-        mlp_update<false>(u, m_off + (o0 + oo) * ncol + col,
-                          Ws[tx * MLP_LD + oo], g[q], k0);
+        mlp_update<CORR>(u, m_off + (o0 + oo) * ncol + col,
+                         Ws[tx * MLP_LD + oo], g[q], kc[q]);
     }
     __syncthreads();
   }
@@ -365,16 +391,18 @@ cnn_fc_bwd_k(const CnnRoundArgs a, int s) {
   __syncthreads();
   if (tid < MLP_TN && j0 + tid < ncol) {     // dbf1 = sum of dz1 over the rows
     const int e = L.fb1 + j0 + tid;
+    const MlpCorr kc = mlp_corr_load<CORR>(u, e);
     float sb = 0.f;
     for (int b = 0; b < a.m.B; ++b) sb += As[b * MLP_LD + tid];
-    mlp_update<false>(u, e, u.p[e], sb, k0);
+    mlp_update<CORR>(u, e, u.p[e], sb, kc);
   }
   if (blockIdx.y == 0) {                     // dbf2 = sum of dl over the rows
     for (int k = tid; k < L.K; k += CNNROUND_THREADS) {
+      const MlpCorr kc = mlp_corr_load<CORR>(u, L.fb2 + k);
       float sb = 0.f;
       for (int b = 0; b < a.m.B; ++b)
         if (rid[b] >= 0) sb += dzM[(long)b * L.K + k];
-      mlp_update<false>(u, L.fb2 + k, u.p[L.fb2 + k], sb, k0);
+      mlp_update<CORR>(u, L.fb2 + k, u.p[L.fb2 + k], sb, kc);
     }
   }
 }
@@ -488,6 +516,9 @@ cnn_conv2_dgrad_k(const CnnRoundArgs a, int s) {
 // + 63 of every channel; the samples are summed in order.  Block 0 also
 // updates b2.  grid = (C, ceil(25 C1 / 64)); dynamic LDS: Dz [64][O2^2 | 1],
 // Ps [C1 S1^2], coff [64], ptab [O2^2], red [256].
+// CORR: the SGD updates take the round's gradient correction, loaded in the
+// epilogue tile by tile.
+template <bool CORR>
 __global__ void __launch_bounds__(CNNROUND_THREADS)
 cnn_conv2_wrw_k(const CnnRoundArgs a, int s) {
   extern __shared__ float cnn_smem[];
@@ -507,8 +538,7 @@ cnn_conv2_wrw_k(const CnnRoundArgs a, int s) {
   float* red = (float*)(ptab + npx);
   const int n0 = blockIdx.y * NC;
   mlp_rows(a.m, c, s, rid);
-  const MlpSgd u = mlp_sgd<false>(a.m, c, s);
-  const MlpCorr k0 = {0.f, 0.f};
+  const MlpSgd u = mlp_sgd<CORR>(a.m, c, s);
   const float* ws = a.m.ws + (long)c * a.m.lay.ws_stride;
   const unsigned char* wsb = a.wsb + (long)c * L.wsb_stride;
   for (int j = tid; j < NC; j += CNNROUND_THREADS) {
@@ -558,15 +588,26 @@ cnn_conv2_wrw_k(const CnnRoundArgs a, int s) {
     }
   }
 #pragma unroll
-  for (int j = 0; j < CNN_WRW_NT; ++j)
+  for (int j = 0; j < CNN_WRW_NT; ++j) {
+    const int n = n0 + 16 * j + lr;
+    // the correction of the tile's four elements, ahead of their updates
+    MlpCorr kc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int co = 16 * w + 4 * lk + i, n = n0 + 16 * j + lr;
+      const int co = 16 * w + 4 * lk + i;
+      kc[i] = MlpCorr{0.f, 0.f};
+      if (co < C2 && n < K2)
+        kc[i] = mlp_corr_load<CORR>(u, L.w2 + co * K2 + n);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int co = 16 * w + 4 * lk + i;
       if (co < C2 && n < K2) {
         const int e = L.w2 + co * K2 + n;
-        mlp_update<false>(u, e, u.p[e], acc[j][i], k0);
+        mlp_update<CORR>(u, e, u.p[e], acc[j][i], kc[i]);
       }
     }
+  }
   if (blockIdx.y != 0) return;
   // db2[co]: wave q sums the samples q, q + 4, ..., the four parts in order
   {
@@ -584,9 +625,10 @@ cnn_conv2_wrw_k(const CnnRoundArgs a, int s) {
   }
   __syncthreads();
   if (tid < C2) {
+    const MlpCorr kb = mlp_corr_load<CORR>(u, L.b2 + tid);
     const float sb = ((red[tid] + red[64 + tid]) + red[128 + tid]) +
                      red[192 + tid];
-    mlp_update<false>(u, L.b2 + tid, u.p[L.b2 + tid], sb, k0);
+    mlp_update<CORR>(u, L.b2 + tid, u.p[L.b2 + tid], sb, kb);
   }
 }
 
@@ -594,7 +636,9 @@ cnn_conv2_wrw_k(const CnnRoundArgs a, int s) {
 // update.  dz1c has one non-zero per pool window, so the sum runs over the
 // windows: thread (t, sl) sums filter element t (t = 25 Cin: the bias) over
 // the windows sl, sl + SL, ... of every sample, the SL parts in order.
-// grid = (C, C1).
+// grid = (C, C1).  CORR: the SGD update takes the round's gradient
+// correction, loaded ahead of the sample loop by the threads that update.
+template <bool CORR>
 __global__ void __launch_bounds__(CNNROUND_THREADS)
 cnn_conv1_wrw_k(const CnnRoundArgs a, int s) {
   __shared__ float img[CNNROUND_MAXCIN * CNNROUND_MAXS * CNNROUND_MAXS];
@@ -610,8 +654,11 @@ cnn_conv1_wrw_k(const CnnRoundArgs a, int s) {
   const int ntp = nt + 1 <= 32 ? 32 : 128, SL = CNNROUND_THREADS / ntp;
   const int t = tid % ntp, sl = tid / ntp;
   mlp_rows(a.m, c, s, rid);
-  const MlpSgd u = mlp_sgd<false>(a.m, c, s);
-  const MlpCorr k0 = {0.f, 0.f};
+  const MlpSgd u = mlp_sgd<CORR>(a.m, c, s);
+  // the correction of the element this thread updates (tid <= nt)
+  MlpCorr kc = {0.f, 0.f};
+  if (CORR && tid <= nt)
+    kc = mlp_corr_load<CORR>(u, tid < nt ? L.w1 + co * nt + tid : L.b1 + co);
   int xo = 0;
   if (t < nt) {
     int ci, tt;
@@ -650,6 +697,6 @@ cnn_conv1_wrw_k(const CnnRoundArgs a, int s) {
     float g = 0.f;
     for (int q = 0; q < SL; ++q) g += part[q * ntp + tid];
     const int e = tid < nt ? L.w1 + co * nt + tid : L.b1 + co;
-    mlp_update<false>(u, e, u.p[e], g, k0);
+    mlp_update<CORR>(u, e, u.p[e], g, kc);
   }
 }

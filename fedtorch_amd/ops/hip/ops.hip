@@ -2640,6 +2640,41 @@ long mlp_round_max_batch() { return MLPROUND_MAXB; }
 long mlp_round_max_classes() { return MLPROUND_MAXK; }
 long mlp_round_max_layers() { return MLPROUND_MAXL; }
 
+// The gradient correction of a layer-batched round (mlp_local_rounds /
+// cnn_local_rounds; an empty tensor: none): checks delta [C, N] or the pair
+// ctrl_server [N] / ctrl_client [C, N] and prox_mu, and fills corr_rows /
+// ctrl_s / prox_mu / corr of `a`.  Nothing is allocated or launched.
+static void round_corr_args(const char* who, MlpRoundArgs& a,
+                            const torch::Tensor& delta,
+                            const torch::Tensor& ctrl_server,
+                            const torch::Tensor& ctrl_client, double prox_mu,
+                            long C, long N, const torch::Device& dev) {
+  const bool has_delta = delta.numel() != 0;
+  const bool has_cs = ctrl_server.numel() != 0;
+  const bool has_cc = ctrl_client.numel() != 0;
+  TORCH_CHECK(has_cs == has_cc, who, ": ctrl_server and ctrl_client come as "
+              "a pair, got only ", has_cs ? "ctrl_server" : "ctrl_client");
+  TORCH_CHECK(!(has_delta && has_cs), who, ": delta and a control pair "
+              "together are not supported (one correction vector per "
+              "client)");
+  if (has_delta)
+    linround_check(who, "delta", delta, torch::kFloat, {C, N}, dev);
+  if (has_cs) {
+    linround_check(who, "ctrl_server", ctrl_server, torch::kFloat, {N}, dev);
+    linround_check(who, "ctrl_client", ctrl_client, torch::kFloat, {C, N},
+                   dev);
+  }
+  TORCH_CHECK(std::isfinite(prox_mu) && prox_mu >= 0.0, who,
+              ": prox_mu must be finite and >= 0, got ", prox_mu);
+  a.corr_rows = has_delta ? delta.data_ptr<float>()
+                : has_cs  ? ctrl_client.data_ptr<float>()
+                          : nullptr;
+  a.ctrl_s = has_cs ? ctrl_server.data_ptr<float>() : nullptr;
+  a.prox_mu = (float)prox_mu;
+  a.corr = (has_delta ? MLPROUND_DELTA : 0) | (has_cs ? MLPROUND_CTRL : 0) |
+           (prox_mu != 0.0 ? MLPROUND_PROX : 0);
+}
+
 // layout: [L, (w, b, gamma, beta, in, out) x L, fc, H, K] -- arena offsets
 // and shapes of the blocks and of the head.  Returns loss [C, T]; writes
 // replicas / in_mom / mom_init / snap rows of the clients with steps > 0.
@@ -2684,23 +2719,9 @@ torch::Tensor mlp_local_rounds(
   const bool has_snap = snap.numel() != 0;
   if (has_snap) linround_check(who, "snap", snap, torch::kFloat, {C, N}, dev);
   // the gradient correction of the round (an empty tensor: none)
-  const bool has_delta = delta.numel() != 0;
-  const bool has_cs = ctrl_server.numel() != 0;
-  const bool has_cc = ctrl_client.numel() != 0;
-  TORCH_CHECK(has_cs == has_cc, who, ": ctrl_server and ctrl_client come as "
-              "a pair, got only ", has_cs ? "ctrl_server" : "ctrl_client");
-  TORCH_CHECK(!(has_delta && has_cs), who, ": delta and a control pair "
-              "together are not supported (one correction vector per "
-              "client)");
-  if (has_delta)
-    linround_check(who, "delta", delta, torch::kFloat, {C, N}, dev);
-  if (has_cs) {
-    linround_check(who, "ctrl_server", ctrl_server, torch::kFloat, {N}, dev);
-    linround_check(who, "ctrl_client", ctrl_client, torch::kFloat, {C, N},
-                   dev);
-  }
-  TORCH_CHECK(std::isfinite(prox_mu) && prox_mu >= 0.0, who,
-              ": prox_mu must be finite and >= 0, got ", prox_mu);
+  MlpRoundArgs a;
+  round_corr_args(who, a, delta, ctrl_server, ctrl_client, prox_mu, C, N,
+                  dev);
   TORCH_CHECK(k_cut >= 0, who, ": k_cut is ", k_cut, ", expected >= 0");
   TORCH_CHECK(!nesterov || (use_mom && dampening == 0.0), who,
               ": nesterov needs a momentum and zero dampening");
@@ -2779,7 +2800,6 @@ torch::Tensor mlp_local_rounds(
   auto ws = torch::empty({C, off}, X.options());
   auto loss = torch::zeros({C, T}, X.options());
 
-  MlpRoundArgs a;
   a.X = X.data_ptr<float>();
   a.Y = Y.data_ptr<int>();
   a.idx = idx.data_ptr<int>();
@@ -2797,13 +2817,6 @@ torch::Tensor mlp_local_rounds(
   a.use_mom = use_mom; a.nesterov = nesterov; a.wd_numel = (int)wd_numel;
   a.wd = (float)weight_decay; a.mom = (float)momentum;
   a.omd = (float)(1.0 - dampening); a.eps = (float)eps;
-  a.corr_rows = has_delta ? delta.data_ptr<float>()
-                : has_cs  ? ctrl_client.data_ptr<float>()
-                          : nullptr;
-  a.ctrl_s = has_cs ? ctrl_server.data_ptr<float>() : nullptr;
-  a.prox_mu = (float)prox_mu;
-  a.corr = (has_delta ? MLPROUND_DELTA : 0) | (has_cs ? MLPROUND_CTRL : 0) |
-           (prox_mu != 0.0 ? MLPROUND_PROX : 0);
   a.lay = lay;
 
   const dim3 blk(MLPROUND_THREADS);
@@ -2860,12 +2873,16 @@ std::vector<int64_t> cnn_round_limits() {
 // fc2.  Returns loss [C, T]; writes replicas / in_mom / mom_init / snap rows
 // of the clients with steps > 0.  idx and steps are range-checked on the host
 // unless the stream is capturing (the kernels never read X outside [0, M)).
+// delta / ctrl_server / ctrl_client / prox_mu: the gradient correction, as in
+// mlp_local_rounds; with one the <CORR = true> kernels run.
 torch::Tensor cnn_local_rounds(
     torch::Tensor X, torch::Tensor Y, torch::Tensor idx, torch::Tensor steps,
     torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,
     torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,
     long k_cut, std::vector<int64_t> layout, long wd_numel,
-    double weight_decay, double momentum, double dampening, bool nesterov) {
+    double weight_decay, double momentum, double dampening, bool nesterov,
+    torch::Tensor delta, torch::Tensor ctrl_server, torch::Tensor ctrl_client,
+    double prox_mu) {
   const char* who = "cnn_local_rounds";
   TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous(), who,
               ": X must be contiguous [M, Cin*S*S] on GPU");
@@ -2896,6 +2913,11 @@ torch::Tensor cnn_local_rounds(
     linround_check(who, "in_mom", in_mom, torch::kFloat, {C, N}, dev);
   const bool has_snap = snap.numel() != 0;
   if (has_snap) linround_check(who, "snap", snap, torch::kFloat, {C, N}, dev);
+  // the gradient correction of the round (an empty tensor: none)
+  CnnRoundArgs a;
+  MlpRoundArgs& m = a.m;
+  round_corr_args(who, m, delta, ctrl_server, ctrl_client, prox_mu, C, N,
+                  dev);
   TORCH_CHECK(k_cut >= 0, who, ": k_cut is ", k_cut, ", expected >= 0");
   TORCH_CHECK(!nesterov || (use_mom && dampening == 0.0), who,
               ": nesterov needs a momentum and zero dampening");
@@ -2986,8 +3008,6 @@ torch::Tensor cnn_local_rounds(
                           X.options().dtype(torch::kUInt8));
   auto loss = torch::zeros({C, T}, X.options());
 
-  CnnRoundArgs a;
-  MlpRoundArgs& m = a.m;
   m.X = X.data_ptr<float>();
   m.Y = Y.data_ptr<int>();
   m.idx = idx.data_ptr<int>();
@@ -3000,13 +3020,11 @@ torch::Tensor cnn_local_rounds(
   m.snap = has_snap ? snap.data_ptr<float>() : nullptr;
   m.loss = loss.data_ptr<float>();
   m.ws = ws.data_ptr<float>();
-  m.corr_rows = nullptr; m.ctrl_s = nullptr;
   m.M = (int)M; m.B = (int)B; m.T = (int)T; m.N = (int)N;
   m.k_cut = (int)std::min<long>(k_cut, 1L << 30);
   m.use_mom = use_mom; m.nesterov = nesterov; m.wd_numel = (int)wd_numel;
   m.wd = (float)weight_decay; m.mom = (float)momentum;
   m.omd = (float)(1.0 - dampening); m.eps = 0.f;
-  m.prox_mu = 0.f; m.corr = 0;
   // what mlp_head_k reads: one block whose activation is fc1's
   m.lay = MlpLayout{};
   m.lay.L = 1;
@@ -3045,16 +3063,31 @@ torch::Tensor cnn_local_rounds(
                        s);
     hipLaunchKernelGGL(mlp_head_k<true>, dim3(Cu), blk, 0, STREAM, m, s,
                        lay.fb2);
-    hipLaunchKernelGGL(cnn_fc_bwd_k<true>, dim3(Cu, tiles(H)), blk, 0, STREAM,
-                       a, s);
-    hipLaunchKernelGGL(cnn_fc_bwd_k<false>, dim3(Cu, tiles(F2)), blk, 0,
-                       STREAM, a, s);
+    // without a correction: the kernels that know none
+    if (m.corr) {
+      hipLaunchKernelGGL((cnn_fc_bwd_k<true, true>), dim3(Cu, tiles(H)), blk,
+                         0, STREAM, a, s);
+      hipLaunchKernelGGL((cnn_fc_bwd_k<false, true>), dim3(Cu, tiles(F2)),
+                         blk, 0, STREAM, a, s);
+    } else {
+      hipLaunchKernelGGL((cnn_fc_bwd_k<true, false>), dim3(Cu, tiles(H)), blk,
+                         0, STREAM, a, s);
+      hipLaunchKernelGGL((cnn_fc_bwd_k<false, false>), dim3(Cu, tiles(F2)),
+                         blk, 0, STREAM, a, s);
+    }
     hipLaunchKernelGGL(cnn_conv2_dgrad_k, dim3(Cu, t16c1, Bu), blk, lds_dg,
                        STREAM, a, s);
-    hipLaunchKernelGGL(cnn_conv2_wrw_k, dim3(Cu, nwrw), blk, lds_wrw, STREAM,
-                       a, s);
-    hipLaunchKernelGGL(cnn_conv1_wrw_k, dim3(Cu, (unsigned)C1), blk, 0,
-                       STREAM, a, s);
+    if (m.corr) {
+      hipLaunchKernelGGL(cnn_conv2_wrw_k<true>, dim3(Cu, nwrw), blk, lds_wrw,
+                         STREAM, a, s);
+      hipLaunchKernelGGL(cnn_conv1_wrw_k<true>, dim3(Cu, (unsigned)C1), blk,
+                         0, STREAM, a, s);
+    } else {
+      hipLaunchKernelGGL(cnn_conv2_wrw_k<false>, dim3(Cu, nwrw), blk, lds_wrw,
+                         STREAM, a, s);
+      hipLaunchKernelGGL(cnn_conv1_wrw_k<false>, dim3(Cu, (unsigned)C1), blk,
+                         0, STREAM, a, s);
+    }
   }
   if (use_mom)
     hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, 1), blk, 0, STREAM, m, 2);

@@ -55,6 +55,11 @@ PACKED_TYPES = ('fedavg', 'fedprox', 'scaffold', 'fedgate')
 # profiles/packed_cnn_notes.md.
 _BATCHED_CNN_ENABLED = \
     os.environ.get('FEDTORCH_PACKED_BATCHED_CNN', '0') == '1'
+# The same batched kernels for fedprox / scaffold / dense fedgate (their
+# gradient-correction term).  A second opt-in on top of the CNN one:
+# ``FEDTORCH_PACKED_BATCHED_CNN_CORR=1``.
+_BATCHED_CNN_CORR_ENABLED = \
+    os.environ.get('FEDTORCH_PACKED_BATCHED_CNN_CORR', '0') == '1'
 
 
 class VirtualGraph(object):
@@ -287,7 +292,8 @@ class ClientPack(object):
 
     def batched_correction(self):
         """The gradient-correction operands of a batched round
-        (ops.linear_local_rounds / ops.mlp_local_rounds) for the pack's
+        (ops.linear_local_rounds / ops.mlp_local_rounds /
+        ops.cnn_local_rounds) for the pack's
         federated type: what `arm_correction` binds client by client in the
         slot loop, as [C, N] rows."""
         t = getattr(self.args, 'federated_type', None)
@@ -429,7 +435,7 @@ class ClientPack(object):
             why.append('model is not the LeNet-style CNN (5x5 convs, 2x2 '
                        'pools, two Linear layers) that fills the arena')
         why += self._run_blockers(
-            getattr(self.args, 'federated_type', None) == 'fedavg')
+            self._batched_type_ok(_BATCHED_CNN_CORR_ENABLED))
         reasons, cached = self._class_loader_blockers(1, ops.CNNROUND_MAXB)
         why += reasons
         if cached and layout is not None:

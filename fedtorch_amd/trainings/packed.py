@@ -146,11 +146,10 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
     ops.linear_local_rounds for a linear model (FEDTORCH_PACKED_BATCHED,
     `ClientPack.batched_eligible`), ops.mlp_local_rounds for an MLP
     (`mlp=True`: FEDTORCH_PACKED_BATCHED_MLP,
-    `ClientPack.mlp_batched_eligible`), either with the gradient correction
-    of the federated type (`ClientPack.batched_correction`);
-    ops.cnn_local_rounds for the LeNet-style CNN (`cnn=True`:
-    FEDTORCH_PACKED_BATCHED_CNN, `ClientPack.cnn_batched_eligible`, FedAvg
-    only).
+    `ClientPack.mlp_batched_eligible`), ops.cnn_local_rounds for the
+    LeNet-style CNN (`cnn=True`: FEDTORCH_PACKED_BATCHED_CNN,
+    `ClientPack.cnn_batched_eligible`); each with the gradient correction of
+    the federated type (`ClientPack.batched_correction`).
 
     The host first walks the counters (`_plan_local_rounds`).  `snap`:
     DRFA's [C, N] snapshot arena, row j receives client j's parameters before
@@ -173,7 +172,7 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
     if cnn:
         loss = ops.cnn_local_rounds(
             *operands, layout=pack.cnn_layout(),
-            wd_numel=client.arena.wd_numel, **sgd)
+            wd_numel=client.arena.wd_numel, **sgd, **corr)
     elif mlp:
         loss = ops.mlp_local_rounds(
             *operands, layout=pack.mlp_layout(), eps=pack.mlp_eps(),

@@ -3,14 +3,18 @@
 (FEDTORCH_PACKED_BATCHED_CNN off: per client and step one eager forward,
 backward and fused SGD launch) against the batched round (on: the clients'
 steps batched per layer by ops.cnn_local_rounds, hip/cnnround.h).  Needs a
-GPU.
+GPU.  --federated_type fedprox | scaffold | fedgate times the same pair with
+the algorithm's gradient correction (FEDTORCH_PACKED_BATCHED_CNN_CORR: both
+flags on against both off).
 
 Configuration: the stock LeNet-style `cnn` on synthetic MNIST, B = 50,
 tau = 10, C in {16, 128} virtual clients on one rank, every client online,
 momentum 0.9 on and off.
 
 Every configuration runs in a process of its own (started from here, one at
-a time): it builds the federation once, warms both paths up, then runs
+a time): it builds the federation once, warms both paths up (with a
+correction at least two rounds each, so that delta and the controls are
+non-zero in the timed rounds), then runs
 --rounds rounds of each path ALTERNATELY; a round is timed wall-clock
 between two device synchronisations (it includes the host's plan walk, the
 aggregation and the replica re-sync, which both paths share).  The range of
@@ -33,16 +37,17 @@ from fedtorch_amd import ops  # noqa: E402
 from fedtorch_amd.parallel import multiclient  # noqa: E402
 
 B, TAU = 50, 10
+TYPES = ('fedavg', 'fedprox', 'scaffold', 'fedgate')
 
 
-def federation(C, momentum):
+def federation(C, momentum, ftype='fedavg'):
     from fedtorch_amd.parameters import get_args
     from fedtorch_amd.nodes import Client
     os.environ['FEDTORCH_SYNTH_SIZE'] = str(C * 500)
     torch.manual_seed(1)
     np.random.seed(1)
     argv = ['-d', 'mnist', '-a', 'cnn', '-f', 'true',
-            '--federated_type', 'fedavg', '--num_comms', '1',
+            '--federated_type', ftype, '--num_comms', '1',
             '--clients_per_rank', str(C), '-b', str(B), '--lr', '0.05',
             '--federated_sync_type', 'local_step', '--local_step', str(TAU),
             '--online_client_rate', '1.0',
@@ -75,6 +80,7 @@ def one_round(client, pack, batched):
     from fedtorch_amd.trainings.packed import \
         train_and_validate_federated_packed
     multiclient._BATCHED_CNN_ENABLED = batched
+    multiclient._BATCHED_CNN_CORR_ENABLED = batched
     assert pack.cnn_batched_eligible() == batched, pack.cnn_batched_blockers()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -102,13 +108,15 @@ def configuration(C, momentum, a):
     if not (torch.cuda.is_available() and ops.hip_available()):
         raise SystemExit('packed_cnn_micro needs a GPU and the built kernel '
                          'pack')
-    tag = 'cnn mnist B=%d tau=%d C=%d momentum=%s' % (
-        B, TAU, C, 'on' if momentum else 'off')
-    client, pack = federation(C, momentum)
+    ftype = a.federated_type
+    tag = 'cnn mnist %s B=%d tau=%d C=%d momentum=%s' % (
+        ftype, B, TAU, C, 'on' if momentum else 'off')
+    client, pack = federation(C, momentum, ftype)
     layout = pack.cnn_layout()
     print('  conv weight order: conv1 %s, conv2 %s' % tuple(
         'nhwc' if layout[k][3] else 'nchw' for k in ('conv1', 'conv2')))
-    for _ in range(max(a.warmup, 1)):
+    # with a correction two rounds at least: the first one's is zero
+    for _ in range(max(a.warmup, 1 if ftype == 'fedavg' else 2)):
         for batched in (False, True):
             one_round(client, pack, batched)
     t = {False: [], True: []}
@@ -123,6 +131,9 @@ def configuration(C, momentum, a):
               'disjoint, below' if max(f) < min(s) else
               'disjoint, above' if min(f) > max(s) else 'overlap',
               statistics.median(s) / statistics.median(f)), flush=True)
+    for name, rows in (('delta', pack.delta), ('ctrl', pack.ctrl)):
+        if rows is not None:
+            assert bool(rows.any()), name + ' is still zero'
     if a.profile:
         profile_round(client, pack)
 
@@ -131,6 +142,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--federated_type', type=str, default='fedavg',
+                    choices=TYPES)
     ap.add_argument('--clients', type=str, default='16,128')
     ap.add_argument('--momentum', type=str, default='on,off')
     ap.add_argument('--profile', action='store_true')
@@ -145,7 +158,8 @@ def main():
         for m in a.momentum.split(','):
             cmd = [sys.executable, os.path.abspath(__file__), '--single',
                    '--clients', C, '--momentum', m, '--rounds',
-                   str(a.rounds), '--warmup', str(a.warmup)]
+                   str(a.rounds), '--warmup', str(a.warmup),
+                   '--federated_type', a.federated_type]
             if a.profile:
                 cmd.append('--profile')
             subprocess.run(cmd, check=True)
