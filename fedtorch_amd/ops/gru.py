@@ -12,9 +12,13 @@ call (``gru_eligible``) is
   reductions outside the sequential chain
   (``dW_hh = dgh^T @ h_prev``, ``db_hh = sum dgh``).
 
+Hidden sizes 65..128 (``gru_wide_eligible``) take the same route over
+``gru_wide_fwd`` / ``gru_wide_bwd`` (hip/gru_wide.h: W_hh resident in
+registers instead of LDS) when ``FEDTORCH_FUSED_GRU_WIDE=1`` is set as well.
+
 Every other call -- the flag off, a CPU tensor, a GRU the kernels do not
-cover -- is exactly ``gru(x, h0)``.  Default OFF; timings against the library
-path: profiles/gru_notes.md.
+cover (hidden_size > 128 among them) -- is exactly ``gru(x, h0)``.  Both
+flags default OFF; timings against the library path: profiles/gru_notes.md.
 
 Numerics.  The fused path computes ``gx`` in fp32 with autocast disabled,
 reads ``weight_hh`` / ``bias_hh`` in their own dtype (bf16 or fp32),
@@ -36,13 +40,38 @@ from torch.autograd.function import once_differentiable
 from fedtorch_amd import ops
 
 _GRU_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU', '0') == '1'
+# second opt-in on top of the first: hidden sizes MAX_H + 1 .. MAX_H_WIDE
+_GRU_WIDE_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU_WIDE', '0') == '1'
 
 MAX_H = 64
+MAX_H_WIDE = 128
 _FLOATS = (torch.bfloat16, torch.float32)
 
 
 def _kernels_active(t):
     return t.is_cuda and ops.hip_available() and not ops.FORCE_EAGER
+
+
+def _seq_forward(ctx, fwd, gx, w_hh, b_hh, h0, need):
+    out, gates = fwd(gx, w_hh, b_hh, h0, need)
+    if need:
+        ctx.save_for_backward(out, gates, w_hh, h0)
+        ctx.b_dtype = b_hh.dtype
+    return out
+
+
+def _seq_backward(ctx, bwd, dout):
+    out, gates, w_hh, h0 = ctx.saved_tensors
+    need_dw, need_db = ctx.needs_input_grad[1:3]
+    if dout.dtype != torch.float32:
+        dout = dout.float()
+    dgx, dgh, dh0 = bwd(dout.contiguous(), out, gates, w_hh, h0)
+    dw = db = None
+    if need_dw:
+        dw = hh_weight_grad(dgh, out, h0).to(w_hh.dtype)
+    if need_db:
+        db = hh_bias_grad(dgh).to(ctx.b_dtype)
+    return dgx, dw, db, dh0, None
 
 
 class _GRUSeqFn(torch.autograd.Function):
@@ -51,27 +80,26 @@ class _GRUSeqFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gx, w_hh, b_hh, h0, need):
-        out, gates = ops._C.gru_fwd(gx, w_hh, b_hh, h0, need)
-        if need:
-            ctx.save_for_backward(out, gates, w_hh, h0)
-            ctx.b_dtype = b_hh.dtype
-        return out
+        return _seq_forward(ctx, ops._C.gru_fwd, gx, w_hh, b_hh, h0, need)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        out, gates, w_hh, h0 = ctx.saved_tensors
-        need_dw, need_db = ctx.needs_input_grad[1:3]
-        if dout.dtype != torch.float32:
-            dout = dout.float()
-        dgx, dgh, dh0 = ops._C.gru_bwd(dout.contiguous(), out, gates, w_hh,
-                                       h0)
-        dw = db = None
-        if need_dw:
-            dw = hh_weight_grad(dgh, out, h0).to(w_hh.dtype)
-        if need_db:
-            db = hh_bias_grad(dgh).to(ctx.b_dtype)
-        return dgx, dw, db, dh0, None
+        return _seq_backward(ctx, ops._C.gru_bwd, dout)
+
+
+class _GRUWideSeqFn(torch.autograd.Function):
+    """the same over gru_wide_fwd / gru_wide_bwd (65 <= H <= 128)"""
+
+    @staticmethod
+    def forward(ctx, gx, w_hh, b_hh, h0, need):
+        return _seq_forward(ctx, ops._C.gru_wide_fwd, gx, w_hh, b_hh, h0,
+                            need)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        return _seq_backward(ctx, ops._C.gru_wide_bwd, dout)
 
 
 def hh_weight_grad(dgh, out, h0):
@@ -87,8 +115,9 @@ def hh_bias_grad(dgh):
     return dgh.sum((0, 1))
 
 
-def gru_eligible(gru, x, h0):
-    """the fused sequence kernels apply to this (GRU, input, hidden) call"""
+def _covered(gru, x, h0, h_min, h_max):
+    """the flag is on and the (GRU, input, hidden) call is one the sequence
+    kernels serve, with h_min <= hidden_size <= h_max"""
     if not (_GRU_ENABLED and isinstance(x, torch.Tensor)
             and isinstance(h0, torch.Tensor) and isinstance(gru, nn.GRU)
             and _kernels_active(x)):
@@ -97,7 +126,7 @@ def gru_eligible(gru, x, h0):
             or not gru.bias or getattr(gru, 'proj_size', 0) != 0:
         return False
     H = gru.hidden_size
-    if not 1 <= H <= MAX_H:
+    if not h_min <= H <= h_max:
         return False
     for p in (gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0,
               gru.bias_hh_l0):
@@ -111,14 +140,32 @@ def gru_eligible(gru, x, h0):
             and tuple(h0.shape) == (1, x.size(0), H))
 
 
+def gru_eligible(gru, x, h0):
+    """the fused sequence kernels apply to this (GRU, input, hidden) call"""
+    return _covered(gru, x, h0, 1, MAX_H)
+
+
+def gru_wide_eligible(gru, x, h0):
+    """the register-resident kernels (MAX_H < hidden_size <= MAX_H_WIDE)
+    apply to this call: the conditions of ``gru_eligible`` with that range,
+    and FEDTORCH_FUSED_GRU_WIDE=1 on top of FEDTORCH_FUSED_GRU=1"""
+    return _GRU_WIDE_ENABLED and _covered(gru, x, h0, MAX_H + 1, MAX_H_WIDE)
+
+
 def gru_seq(gru, x, h0):
     """``gru(x, h0)`` -> ``(out [B, T, H], h_n [1, B, H])``.  With
     FEDTORCH_FUSED_GRU=1 and an eligible call (GPU, one unidirectional
     batch_first layer with biases, hidden_size <= 64, bf16/fp32 contiguous
     parameters, x [B, T, I], h0 [1, B, H]) the T steps are one gru_fwd
     launch, in training and eval; ``out`` and ``h_n = out[:, -1]`` are then
-    fp32 whatever autocast says (module docstring)."""
-    if not (_GRU_ENABLED and gru_eligible(gru, x, h0)):
+    fp32 whatever autocast says (module docstring).  With
+    FEDTORCH_FUSED_GRU_WIDE=1 as well, 65 <= hidden_size <= 128 takes the
+    same route over gru_wide_fwd / gru_wide_bwd."""
+    if gru_eligible(gru, x, h0):
+        fn = _GRUSeqFn
+    elif gru_wide_eligible(gru, x, h0):
+        fn = _GRUWideSeqFn
+    else:
         return gru(x, h0)
     with torch.autocast(device_type='cuda', enabled=False):
         gx = F.linear(x.float(), gru.weight_ih_l0.float(),
@@ -127,5 +174,5 @@ def gru_seq(gru, x, h0):
                 h0[0].float().contiguous())
         # the gates are stored only where a backward can follow
         need = torch.is_grad_enabled() and any(t.requires_grad for t in args)
-        out = _GRUSeqFn.apply(*args, need)
+        out = fn.apply(*args, need)
     return out, out[:, -1].unsqueeze(0)

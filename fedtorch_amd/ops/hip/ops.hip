@@ -20,6 +20,7 @@
 #include "convs2bwd.h"
 #include "head.h"
 #include "gru.h"
+#include "gru_wide.h"
 #include "linearround.h"
 #include "mlpround.h"
 #include "cnnround.h"
@@ -2474,6 +2475,92 @@ std::vector<torch::Tensor> gru_bwd(torch::Tensor dout, torch::Tensor out,
   return {dgx, dgh, dh0};
 }
 
+// --------------------------------------------------------------------------
+// 65 <= H <= 128: W_hh fragments resident in registers (gru_wide.h).  Operand
+// contracts, checks and return layouts are those of gru_fwd / gru_bwd.
+// --------------------------------------------------------------------------
+static void gru_wide_check_dims(const char* who, long B, long T, long H) {
+  TORCH_CHECK(H >= GRU_WIDE_MINH && H <= GRU_WIDE_MAXH, who,
+              ": unsupported H=", H, " (65 <= H <= 128)");
+  TORCH_CHECK(B >= 1 && T >= 1, who, ": empty input");
+  TORCH_CHECK(B < (1L << 31) && T < (1L << 31) &&
+                  B * T < (1L << 40), who, ": input too large");
+}
+
+std::vector<torch::Tensor> gru_wide_fwd(torch::Tensor gx, torch::Tensor w_hh,
+                                        torch::Tensor b_hh, torch::Tensor h0,
+                                        bool save_gates) {
+  const char* who = "gru_wide_fwd";
+  TORCH_CHECK(gx.is_cuda() && gx.dim() == 3 && gx.is_contiguous(), who,
+              ": gx must be contiguous [B, T, 3H] on GPU");
+  TORCH_CHECK(gx.scalar_type() == torch::kFloat, who, ": gx must be fp32");
+  TORCH_CHECK(gx.size(2) % 3 == 0, who, ": gx is ", gx.sizes(),
+              ", expected [B, T, 3H]");
+  const long B = gx.size(0), T = gx.size(1), H = gx.size(2) / 3;
+  gru_wide_check_dims(who, B, T, H);
+  const auto dev = gx.device();
+  gru_check_param(who, "w_hh", w_hh, {3 * H, H}, dev);
+  gru_check_param(who, "b_hh", b_hh, {3 * H}, dev);
+  gru_check_f32(who, "h0", h0, {B, H}, dev);
+  auto out = torch::empty({B, T, H}, gx.options());
+  auto gates = save_gates ? torch::empty({B, T, 4, H}, gx.options())
+                          : torch::empty({0}, gx.options());
+  const int wbf = w_hh.scalar_type() == torch::kBFloat16;
+  const int bbf = b_hh.scalar_type() == torch::kBFloat16;
+  const unsigned grid = (unsigned)((B + GRU_ROWS - 1) / GRU_ROWS);
+#define GRU_FWD_LAUNCH(NT)                                                   \
+  hipLaunchKernelGGL(gru_fwd_reg_k<NT>, dim3(grid), dim3(NT * WAVE), 0,      \
+                     STREAM, gx.data_ptr<float>(), w_hh.data_ptr(), wbf,     \
+                     b_hh.data_ptr(), bbf, h0.data_ptr<float>(),             \
+                     out.data_ptr<float>(),                                  \
+                     save_gates ? gates.data_ptr<float>() : nullptr, (int)B, \
+                     (int)T, (int)H)
+  switch ((H + 15) / 16) {
+    case 5: GRU_FWD_LAUNCH(5); break;
+    case 6: GRU_FWD_LAUNCH(6); break;
+    case 7: GRU_FWD_LAUNCH(7); break;
+    default: GRU_FWD_LAUNCH(8); break;
+  }
+#undef GRU_FWD_LAUNCH
+  return {out, gates};
+}
+
+std::vector<torch::Tensor> gru_wide_bwd(torch::Tensor dout, torch::Tensor out,
+                                        torch::Tensor gates,
+                                        torch::Tensor w_hh, torch::Tensor h0) {
+  const char* who = "gru_wide_bwd";
+  TORCH_CHECK(out.is_cuda() && out.dim() == 3 && out.is_contiguous(), who,
+              ": out must be contiguous [B, T, H] on GPU");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat, who, ": out must be fp32");
+  const long B = out.size(0), T = out.size(1), H = out.size(2);
+  gru_wide_check_dims(who, B, T, H);
+  const auto dev = out.device();
+  gru_check_f32(who, "dout", dout, {B, T, H}, dev);
+  gru_check_f32(who, "gates", gates, {B, T, 4, H}, dev);
+  gru_check_param(who, "w_hh", w_hh, {3 * H, H}, dev);
+  gru_check_f32(who, "h0", h0, {B, H}, dev);
+  auto dgx = torch::empty({B, T, 3 * H}, out.options());
+  auto dgh = torch::empty({B, T, 3 * H}, out.options());
+  auto dh0 = torch::empty({B, H}, out.options());
+  const int wbf = w_hh.scalar_type() == torch::kBFloat16;
+  const unsigned grid = (unsigned)((B + GRU_ROWS - 1) / GRU_ROWS);
+#define GRU_BWD_LAUNCH(NT)                                                   \
+  hipLaunchKernelGGL(gru_bwd_reg_k<NT>, dim3(grid), dim3(NT * WAVE), 0,      \
+                     STREAM, dout.data_ptr<float>(), out.data_ptr<float>(),  \
+                     gates.data_ptr<float>(), w_hh.data_ptr(), wbf,          \
+                     h0.data_ptr<float>(), dgx.data_ptr<float>(),            \
+                     dgh.data_ptr<float>(), dh0.data_ptr<float>(), (int)B,   \
+                     (int)T, (int)H)
+  switch ((H + 15) / 16) {
+    case 5: GRU_BWD_LAUNCH(5); break;
+    case 6: GRU_BWD_LAUNCH(6); break;
+    case 7: GRU_BWD_LAUNCH(7); break;
+    default: GRU_BWD_LAUNCH(8); break;
+  }
+#undef GRU_BWD_LAUNCH
+  return {dgx, dgh, dh0};
+}
+
 // ==========================================================================
 // packed linear models: all clients' local steps in one launch
 // (linearround.h)
@@ -3106,6 +3193,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_round_lds_floats", &linear_round_lds_floats);
   m.def("gru_fwd", &gru_fwd);
   m.def("gru_bwd", &gru_bwd);
+  m.def("gru_wide_fwd", &gru_wide_fwd);
+  m.def("gru_wide_bwd", &gru_wide_bwd);
   m.def("head_fwd", &head_fwd);
   m.def("head_bwd", &head_bwd);
   m.def("ce_topk_accum", &ce_topk_accum);

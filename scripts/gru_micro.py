@@ -1,12 +1,15 @@
 # -*- coding: utf-8 -*-
 """Char-GRU sequence layer: FEDTORCH_FUSED_GRU off (nn.GRU, the library RNN
 path) vs on (one F.linear + the persistent gru_fwd / gru_bwd kernels of
-hip/gru.h).  Needs a GPU.
+hip/gru.h).  With --hidden 65..128 --wide 1 the fused setting also turns on
+FEDTORCH_FUSED_GRU_WIDE (gru_wide_fwd / gru_wide_bwd of hip/gru_wide.h).
+Needs a GPU.
 
-(a) per call: forward + backward of the GRU layer alone (fp32, H = 50,
-    T = 50, B in {10, 50, 128}; gradients of x, h0 and the four parameters).
-(b) one full CharGRU train step each way (vocab 86, H = 50, T = 50, B = 10):
-    forward, cross-entropy, backward, SGD step.
+(a) per call: forward + backward of the GRU layer alone (fp32, H = --hidden
+    (default 50), T = 50, B in {10, 50, 128}; gradients of x, h0 and the
+    four parameters).
+(b) one full CharGRU train step each way (vocab 86, the same H, T = 50,
+    B = 10): forward, cross-entropy, backward, SGD step.
 (c) kernel launches per call of (a) and per step of (b), counted with the
     torch profiler (device-kernel events; memcpy / memset listed apart).
 
@@ -78,6 +81,11 @@ def launches(fn):
         return 'unavailable (%s)' % type(e).__name__, None
 
 
+def set_flags(flag, a):
+    fgru._GRU_ENABLED = flag
+    fgru._GRU_WIDE_ENABLED = flag and bool(a.wide)
+
+
 def compare(tag, call, a):
     for _name, flag in SETTINGS:                 # warm up ALL first
         for _ in range(a.warmup):
@@ -94,6 +102,7 @@ def compare(tag, call, a):
 
 
 def layer(a):
+    H = a.hidden
     for B in (10, 50, 128):
         torch.manual_seed(B)
         gru = nn.GRU(H, H, batch_first=True).cuda()
@@ -103,7 +112,7 @@ def layer(a):
         leaves = (x, h0) + tuple(gru.parameters())
 
         def call(flag):
-            fgru._GRU_ENABLED = flag
+            set_flags(flag, a)
             out, _hn = fgru.gru_seq(gru, x, h0)
             torch.autograd.grad(out, leaves, dout)
 
@@ -111,7 +120,7 @@ def layer(a):
 
 
 def train_step(a):
-    B = 10
+    B, H = 10, a.hidden
     torch.manual_seed(1)
     models, opts = {}, {}
     for name, _flag in SETTINGS:
@@ -123,7 +132,7 @@ def train_step(a):
     names = {flag: name for name, flag in SETTINGS}
 
     def call(flag):
-        fgru._GRU_ENABLED = flag
+        set_flags(flag, a)
         m, opt = models[names[flag]], opts[names[flag]]
         opt.zero_grad(set_to_none=True)
         F.cross_entropy(m(x), y).backward()
@@ -138,15 +147,20 @@ def main():
     ap.add_argument('--samples', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--launches', type=int, default=1)
+    ap.add_argument('--hidden', type=int, default=H)
+    ap.add_argument('--wide', type=int, default=0)
     a = ap.parse_args()
+    if a.hidden > (fgru.MAX_H_WIDE if a.wide else fgru.MAX_H):
+        raise SystemExit('H = %d is the library path either way (--wide 1 '
+                         'covers 65..128)' % a.hidden)
     if not (torch.cuda.is_available() and ops.hip_available()):
         raise SystemExit('gru_micro needs a GPU and the built kernel pack')
-    old = fgru._GRU_ENABLED
+    old = fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED
     try:
         layer(a)
         train_step(a)
     finally:
-        fgru._GRU_ENABLED = old
+        fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED = old
     print('GRU_MICRO_OK')
 
 
