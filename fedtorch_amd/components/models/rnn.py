@@ -7,7 +7,7 @@ whenever the batch size changes.
 """
 import torch.nn as nn
 
-from fedtorch_amd.ops.gru import gru_seq
+from fedtorch_amd.ops.gru import gru_seq, gru_tok_eligible, gru_tok_seq
 
 
 class CharGRU(nn.Module):
@@ -40,8 +40,13 @@ class CharGRU(nn.Module):
             self.init_hidden(x.size(0))
         if self.hidden.device != x.device:
             self.hidden = self.hidden.to(x.device)
-        emb = self.encoder(x)
-        out, h = gru_seq(self.gru, emb, self.hidden.detach())
+        hidden = self.hidden.detach()
+        if gru_tok_eligible(self.encoder, self.gru, x, hidden):
+            # the embedding rows are gathered inside the sequence kernel
+            out, h = gru_tok_seq(self.encoder, self.gru, x, hidden)
+        else:
+            emb = self.encoder(x)
+            out, h = gru_seq(self.gru, emb, hidden)
         self.hidden = h.detach()
         out = self.decoder(out)
         # (B, C, T) for CrossEntropyLoss over characters

@@ -20,6 +20,21 @@ Every other call -- the flag off, a CPU tensor, a GRU the kernels do not
 cover (hidden_size > 128 among them) -- is exactly ``gru(x, h0)``.  Both
 flags default OFF; timings against the library path: profiles/gru_notes.md.
 
+Token input (``gru_tok_seq(encoder, gru, tok, h0)``, third opt-in
+``FEDTORCH_FUSED_GRU_TOKENS=1`` on top of the flags above, default OFF).  When
+the layer's input is ``encoder(tok)`` for a plain ``nn.Embedding``,
+``gx[b, t]`` is one of the V rows of ``P = E W_ih^T + b_ih``.  An eligible
+call (``gru_tok_eligible``) is one ``addmm`` over V rows (library autograd:
+``dE``, ``dW_ih``, ``db_ih`` from ``dP``), ONE ``gru_tok_fwd`` /
+``gru_tok_wide_fwd`` launch that gathers ``P[tok]`` inside the sequence
+kernel, and in training the unchanged ``gru_bwd`` / ``gru_wide_bwd`` plus ONE
+``gru_tok_grads`` launch for ``dP``, ``dW_hh`` and ``db_hh`` (hip/gru_tok.h).
+``emb``, ``gx`` and the concatenated ``h_prev`` are never materialised.  A
+token outside ``[0, V)`` -- on which ``nn.Embedding`` faults -- reads
+``gx = 0`` and contributes nothing to ``dP``: the launchers never read ``tok``
+on the host.  An infinite ``dgx`` element turns its column of the whole
+16-row vocabulary tile of ``dP`` into NaN (0 * inf in the one-hot product).
+
 Numerics.  The fused path computes ``gx`` in fp32 with autocast disabled,
 reads ``weight_hh`` / ``bias_hh`` in their own dtype (bf16 or fp32),
 accumulates in fp32 and returns **fp32** ``out`` and ``h_n`` whatever
@@ -42,6 +57,8 @@ from fedtorch_amd import ops
 _GRU_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU', '0') == '1'
 # second opt-in on top of the first: hidden sizes MAX_H + 1 .. MAX_H_WIDE
 _GRU_WIDE_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU_WIDE', '0') == '1'
+# third opt-in on top of those: token input through the [V, 3H] table
+_GRU_TOK_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU_TOKENS', '0') == '1'
 
 MAX_H = 64
 MAX_H_WIDE = 128
@@ -102,6 +119,53 @@ class _GRUWideSeqFn(torch.autograd.Function):
         return _seq_backward(ctx, ops._C.gru_wide_bwd, dout)
 
 
+def _tok_forward(ctx, fwd, P, tok, w_hh, b_hh, h0, need):
+    out, gates = fwd(P, tok, w_hh, b_hh, h0, need)
+    if need:
+        ctx.save_for_backward(out, gates, w_hh, h0, tok)
+        ctx.vocab = P.size(0)
+        ctx.b_dtype = b_hh.dtype
+    return out
+
+
+def _tok_backward(ctx, bwd, dout):
+    out, gates, w_hh, h0, tok = ctx.saved_tensors
+    if dout.dtype != torch.float32:
+        dout = dout.float()
+    dgx, dgh, dh0 = bwd(dout.contiguous(), out, gates, w_hh, h0)
+    dP, dw, db = ops._C.gru_tok_grads(dgx, dgh, out, h0, tok, ctx.vocab)
+    return dP, None, dw.to(w_hh.dtype), db.to(ctx.b_dtype), dh0, None
+
+
+class _GRUTokSeqFn(torch.autograd.Function):
+    """_GRUSeqFn with gx[b, t] = P[tok[b, t]]: P [V, 3H] fp32, tok [B, T]
+    int64; backward is gru_bwd, then gru_tok_grads for dP, dW_hh, db_hh"""
+
+    @staticmethod
+    def forward(ctx, P, tok, w_hh, b_hh, h0, need):
+        return _tok_forward(ctx, ops._C.gru_tok_fwd, P, tok, w_hh, b_hh, h0,
+                            need)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        return _tok_backward(ctx, ops._C.gru_bwd, dout)
+
+
+class _GRUTokWideSeqFn(torch.autograd.Function):
+    """the same over gru_tok_wide_fwd / gru_wide_bwd (65 <= H <= 128)"""
+
+    @staticmethod
+    def forward(ctx, P, tok, w_hh, b_hh, h0, need):
+        return _tok_forward(ctx, ops._C.gru_tok_wide_fwd, P, tok, w_hh, b_hh,
+                            h0, need)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        return _tok_backward(ctx, ops._C.gru_wide_bwd, dout)
+
+
 def hh_weight_grad(dgh, out, h0):
     """dW_hh [3H, H] = dgh^T @ h_prev with h_prev = (h0, out[:, :-1]): one
     deterministic fp32 library GEMM outside the sequential chain"""
@@ -115,9 +179,10 @@ def hh_bias_grad(dgh):
     return dgh.sum((0, 1))
 
 
-def _covered(gru, x, h0, h_min, h_max):
-    """the flag is on and the (GRU, input, hidden) call is one the sequence
-    kernels serve, with h_min <= hidden_size <= h_max"""
+def _gru_covered(gru, x, h0, h_min, h_max):
+    """the flag is on and the GRU and hidden state are ones the sequence
+    kernels serve, with h_min <= hidden_size <= h_max, for an input tensor
+    ``x`` (floats [B, T, I] or tokens [B, T]) whose device decides"""
     if not (_GRU_ENABLED and isinstance(x, torch.Tensor)
             and isinstance(h0, torch.Tensor) and isinstance(gru, nn.GRU)
             and _kernels_active(x)):
@@ -133,11 +198,18 @@ def _covered(gru, x, h0, h_min, h_max):
         if p.device != x.device or p.dtype not in _FLOATS \
                 or not p.is_contiguous():
             return False
-    if x.dim() != 3 or not x.is_floating_point() or x.numel() == 0 \
-            or x.size(2) != gru.input_size:
-        return False
-    return (h0.device == x.device and h0.is_floating_point()
+    return (x.dim() >= 1 and h0.device == x.device
+            and h0.is_floating_point()
             and tuple(h0.shape) == (1, x.size(0), H))
+
+
+def _covered(gru, x, h0, h_min, h_max):
+    """the flag is on and the (GRU, input, hidden) call is one the sequence
+    kernels serve, with h_min <= hidden_size <= h_max"""
+    if not _gru_covered(gru, x, h0, h_min, h_max):
+        return False
+    return (x.dim() == 3 and x.is_floating_point() and x.numel() > 0
+            and x.size(2) == gru.input_size)
 
 
 def gru_eligible(gru, x, h0):
@@ -171,6 +243,62 @@ def gru_seq(gru, x, h0):
         gx = F.linear(x.float(), gru.weight_ih_l0.float(),
                       gru.bias_ih_l0.float())
         args = (gx.contiguous(), gru.weight_hh_l0, gru.bias_hh_l0,
+                h0[0].float().contiguous())
+        # the gates are stored only where a backward can follow
+        need = torch.is_grad_enabled() and any(t.requires_grad for t in args)
+        out = fn.apply(*args, need)
+    return out, out[:, -1].unsqueeze(0)
+
+
+def _tok_fn(gru, tok, h0):
+    """the autograd function of the token path for this GRU, or None"""
+    if not _GRU_TOK_ENABLED:
+        return None
+    if _gru_covered(gru, tok, h0, 1, MAX_H):
+        return _GRUTokSeqFn
+    if _GRU_WIDE_ENABLED and _gru_covered(gru, tok, h0, MAX_H + 1,
+                                          MAX_H_WIDE):
+        return _GRUTokWideSeqFn
+    return None
+
+
+def gru_tok_eligible(encoder, gru, tok, h0):
+    """the token path applies to ``gru(encoder(tok), h0)``:
+    FEDTORCH_FUSED_GRU_TOKENS=1 on top of the conditions of ``gru_eligible``
+    / ``gru_wide_eligible`` for the GRU and h0; ``tok`` a non-empty int64
+    [B, T] tensor on the GPU; ``encoder`` a plain ``nn.Embedding`` (no
+    padding_idx, max_norm, sparse or scale_grad_by_freq) with a contiguous
+    fp32 / bf16 weight on that device and embedding_dim == gru.input_size"""
+    if _tok_fn(gru, tok, h0) is None:
+        return False
+    if tok.dtype != torch.int64 or tok.dim() != 2 or tok.numel() == 0:
+        return False
+    if type(encoder) is not nn.Embedding or encoder.padding_idx is not None \
+            or encoder.max_norm is not None or encoder.sparse \
+            or encoder.scale_grad_by_freq:
+        return False
+    E = encoder.weight
+    return (E.device == tok.device and E.dtype in _FLOATS
+            and E.is_contiguous()
+            and encoder.embedding_dim == gru.input_size)
+
+
+def gru_tok_seq(encoder, gru, tok, h0):
+    """``gru(encoder(tok), h0)`` -> ``(out [B, T, H], h_n [1, B, H])``.  An
+    eligible call (``gru_tok_eligible``) never builds ``encoder(tok)`` or
+    ``gx``: one addmm makes the table P = E W_ih^T + b_ih [V, 3H], one
+    gru_tok_fwd / gru_tok_wide_fwd launch runs the T steps on P[tok], and
+    backward is gru_bwd / gru_wide_bwd plus one gru_tok_grads launch; ``out``
+    and ``h_n`` are fp32 as in ``gru_seq``.  A token outside [0, V) reads
+    gx = 0 there (module docstring).  Anything else is
+    ``gru_seq(gru, encoder(tok), h0)``."""
+    if not gru_tok_eligible(encoder, gru, tok, h0):
+        return gru_seq(gru, encoder(tok), h0)
+    fn = _tok_fn(gru, tok, h0)
+    with torch.autocast(device_type='cuda', enabled=False):
+        P = torch.addmm(gru.bias_ih_l0.float(), encoder.weight.float(),
+                        gru.weight_ih_l0.float().t())
+        args = (P, tok.contiguous(), gru.weight_hh_l0, gru.bias_hh_l0,
                 h0[0].float().contiguous())
         # the gates are stored only where a backward can follow
         need = torch.is_grad_enabled() and any(t.requires_grad for t in args)

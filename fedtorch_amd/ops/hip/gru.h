@@ -38,6 +38,17 @@
 // (b >= B) and pad columns (>= H) are never loaded and never stored; they
 // carry zeros through the LDS operands.
 //
+// Token variant (TOK = true, gru_tok_fwd): the layer's input is a token id, so
+// gx[b, t] is one of the V rows of the table P = E W_ih^T + b_ih [V, 3H].  The
+// forward kernels then take P in place of gx and read row tok[b, t] of it:
+// the only difference is the address.  That makes the per-step prefetch a
+// dependent pair (token, then table row), so the tokens run one step further
+// ahead: while the table rows of step t + 1 are in flight the four row tokens
+// of step t + 2 are loaded, and neither load is waited for before the MFMAs.
+// A token outside [0, V) is never used as an address: that position reads
+// gx = 0.  gru_fwd_k and gru_tok_fwd_k share one text (gru_fwd_k.inc); TOK =
+// false is the float-input kernel, instruction for instruction.
+//
 // Limits (checked by the launchers): 1 <= H <= 64, T >= 1, B >= 1.
 // LDS row strides are chosen so that the ds_read_b32 operand fetches (banks
 // = dword address mod 32 within each half wave) are conflict-free.
@@ -51,6 +62,15 @@
 
 typedef float gru_f4 __attribute__((ext_vector_type(4)));
 
+// scalar fp32 code only: independent per-lane elements may otherwise be paired
+// into packed fp32 operations (a device feature: the host pass does not know
+// it)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GRU_SCALAR_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define GRU_SCALAR_F32
+#endif
+
 __device__ __forceinline__ float gru_ld1(const void* p, long i, int bf16) {
   return bf16 ? __bfloat162float(
                     reinterpret_cast<const __hip_bfloat16*>(p)[i])
@@ -59,117 +79,24 @@ __device__ __forceinline__ float gru_ld1(const void* p, long i, int bf16) {
 __device__ __forceinline__ float gru_sigmoid(float a) {
   return 1.f / (1.f + expf(-a));
 }
+// Offset of table row tok[i] in P [V, H3], or -1 where the load is off or the
+// token is outside [0, V): such a position reads gx = 0.
+__device__ __forceinline__ int gru_tok_off(const long* __restrict__ tok,
+                                           long i, bool ld, int V, int H3) {
+  if (!ld) return -1;
+  const long v = tok[i];
+  return (v >= 0 && v < V) ? (int)v * H3 : -1;
+}
 
 // --------------------------------------------------------------------------
 // forward
 // --------------------------------------------------------------------------
-// grid ceil(B/16), block 64*NT.  gates [B, T, 4, H] = (r, z, n, q) or null.
-template <int NT>
-__global__ void __launch_bounds__(NT * WAVE)
-gru_fwd_k(const float* __restrict__ gx, const void* __restrict__ w,
-          int w_bf16, const void* __restrict__ bias, int b_bf16,
-          const float* __restrict__ h0, float* __restrict__ out,
-          float* __restrict__ gates, int B, int T, int H) {
-  constexpr int HP = NT * 16;
-  constexpr int S = HP + 2;             // S mod 32 in {2, 18}
-  constexpr int NTHR = NT * WAVE;
-  __shared__ float Ws[3 * HP * S];      // [gate][n][k]
-  __shared__ float hs[2][GRU_ROWS * S];  // [buffer][row][k]
-  const int tid = threadIdx.x;
-  const int lane = tid & (WAVE - 1), wid = tid / WAVE;
-  const int lr = lane & 15, lk = lane >> 4;
-  const long b0 = (long)blockIdx.x * GRU_ROWS;
-
-  for (int i = tid; i < 3 * HP * S; i += NTHR) {
-    const int g = i / (HP * S), rem = i - g * (HP * S);
-    const int n = rem / S, k = rem - n * S;
-    Ws[i] = (n < H && k < H) ? gru_ld1(w, ((long)g * H + n) * H + k, w_bf16)
-                             : 0.f;
-  }
-  for (int i = tid; i < GRU_ROWS * S; i += NTHR) {
-    const int m = i / S, k = i - m * S;
-    hs[0][i] = (b0 + m < B && k < H) ? h0[(b0 + m) * H + k] : 0.f;
-    hs[1][i] = 0.f;
-  }
-
-  const int col = wid * 16 + lr;        // hidden column of this lane
-  const bool lcol = col < H;
-  bool live[4];
-  long ob[4];                           // (b*T)*H + col
-  float hprev[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const long b = b0 + 4 * lk + i;
-    live[i] = lcol && b < B;
-    ob[i] = b * T * (long)H + col;
-    hprev[i] = live[i] ? h0[b * H + col] : 0.f;
-  }
-  const float br = lcol ? gru_ld1(bias, col, b_bf16) : 0.f;
-  const float bz = lcol ? gru_ld1(bias, H + col, b_bf16) : 0.f;
-  const float bn = lcol ? gru_ld1(bias, 2 * H + col, b_bf16) : 0.f;
-
-  float xr[4], xz[4], xn[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float* p = gx + ob[i] * 3 - 2 * col;   // (b*T + 0)*3H + col
-    xr[i] = live[i] ? p[0] : 0.f;
-    xz[i] = live[i] ? p[H] : 0.f;
-    xn[i] = live[i] ? p[2 * H] : 0.f;
-  }
-  __syncthreads();
-
-  const float* wr = Ws + (0 * HP + col) * S + lk;
-  const float* wz = Ws + (1 * HP + col) * S + lk;
-  const float* wn = Ws + (2 * HP + col) * S + lk;
-  for (int t = 0; t < T; ++t) {
-    const int cur = t & 1;
-    // next step's input projection, in flight during the MFMAs
-    float yr[4], yz[4], yn[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool ld = live[i] && t + 1 < T;
-      const float* p = gx + (ob[i] + (long)(t + 1) * H) * 3 - 2 * col;
-      yr[i] = ld ? p[0] : 0.f;
-      yz[i] = ld ? p[H] : 0.f;
-      yn[i] = ld ? p[2 * H] : 0.f;
-    }
-    gru_f4 ar = {br, br, br, br}, az = {bz, bz, bz, bz},
-           an = {bn, bn, bn, bn};
-    const float* ha = hs[cur] + lr * S + lk;
-#pragma unroll
-    for (int kk = 0; kk < HP / 4; ++kk) {
-      const float a = ha[kk * 4];
-      ar = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wr[kk * 4], ar, 0, 0, 0);
-      az = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wz[kk * 4], az, 0, 0, 0);
-      an = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wn[kk * 4], an, 0, 0, 0);
-    }
-    float* hn = hs[cur ^ 1] + (4 * lk) * S + col;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float r = gru_sigmoid(xr[i] + ar[i]);
-      const float z = gru_sigmoid(xz[i] + az[i]);
-      const float q = an[i];
-      const float n = tanhf(xn[i] + r * q);
-      float h = (1.f - z) * n + z * hprev[i];
-      if (!live[i]) h = 0.f;
-      hn[i * S] = h;
-      hprev[i] = h;
-      if (live[i]) {
-        const long o = ob[i] + (long)t * H;
-        out[o] = h;
-        if (gates) {
-          float* gp = gates + o * 4 - 3 * col;   // ((b*T + t)*4)*H + col
-          gp[0] = r;
-          gp[H] = z;
-          gp[2 * H] = n;
-          gp[3 * H] = q;
-        }
-      }
-      xr[i] = yr[i]; xz[i] = yz[i]; xn[i] = yn[i];
-    }
-    __syncthreads();
-  }
-}
+#define GRU_FWD_TOK 0
+#include "gru_fwd_k.inc"
+#undef GRU_FWD_TOK
+#define GRU_FWD_TOK 1
+#include "gru_fwd_k.inc"
+#undef GRU_FWD_TOK
 
 // --------------------------------------------------------------------------
 // backward

@@ -45,11 +45,7 @@
 // scalar fp32 code only: the gate math below is four independent elements per
 // lane, which the compiler may otherwise pair into packed fp32 operations
 // (a device feature: the host pass does not know it)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define GRU_WIDE_KERNEL __attribute__((target("no-packed-fp32-ops")))
-#else
-#define GRU_WIDE_KERNEL
-#endif
+#define GRU_WIDE_KERNEL GRU_SCALAR_F32
 
 // One lane's B fragments of the three gate blocks: dst[g][kk] =
 // w[(g H + row0 + kk rstep) H + col0 + kk cstep] where that element exists,
@@ -74,12 +70,15 @@ __device__ __forceinline__ GRU_WIDE_KERNEL void gru_wide_frag(
 // forward
 // --------------------------------------------------------------------------
 // grid ceil(B/16), block 64*NT.  gates [B, T, 4, H] = (r, z, n, q) or null.
-template <int NT>
+// TOK (gru_tok_wide_fwd): gx is the table P [V, 3H] and tok [B, T] selects its
+// rows, prefetched as in gru_fwd_k; else tok and V are unused.
+template <int NT, bool TOK>
 __global__ void __launch_bounds__(NT * WAVE) GRU_WIDE_KERNEL
 gru_fwd_reg_k(const float* __restrict__ gx, const void* __restrict__ w,
               int w_bf16, const void* __restrict__ bias, int b_bf16,
               const float* __restrict__ h0, float* __restrict__ out,
-              float* __restrict__ gates, int B, int T, int H) {
+              float* __restrict__ gates, int B, int T, int H,
+              const long* __restrict__ tok, int V) {
   constexpr int HP = NT * 16;
   constexpr int KK = HP / 4;
   constexpr int S = HP + 2;             // S mod 32 in {2, 18}
@@ -120,12 +119,23 @@ gru_fwd_reg_k(const float* __restrict__ gx, const void* __restrict__ w,
   const float bn = lcol ? gru_ld1(bias, 2 * H + col, b_bf16) : 0.f;
 
   float xr[4], xz[4], xn[4];
+  int tk[4];                            // TOK: P offset of step t + 1, or -1
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const float* p = gx + ob[i] * 3 - 2 * col;   // (b*T + 0)*3H + col
-    xr[i] = live[i] ? p[0] : 0.f;
-    xz[i] = live[i] ? p[H] : 0.f;
-    xn[i] = live[i] ? p[2 * H] : 0.f;
+    if constexpr (TOK) {
+      const long ti = (b0 + 4 * lk + i) * T;
+      const int o = gru_tok_off(tok, ti, live[i], V, 3 * H);
+      tk[i] = gru_tok_off(tok, ti + 1, live[i] && 1 < T, V, 3 * H);
+      const float* p = gx + o + col;
+      xr[i] = o >= 0 ? p[0] : 0.f;
+      xz[i] = o >= 0 ? p[H] : 0.f;
+      xn[i] = o >= 0 ? p[2 * H] : 0.f;
+    } else {
+      const float* p = gx + ob[i] * 3 - 2 * col;   // (b*T + 0)*3H + col
+      xr[i] = live[i] ? p[0] : 0.f;
+      xz[i] = live[i] ? p[H] : 0.f;
+      xn[i] = live[i] ? p[2 * H] : 0.f;
+    }
   }
   __syncthreads();
 
@@ -133,13 +143,24 @@ gru_fwd_reg_k(const float* __restrict__ gx, const void* __restrict__ w,
     const int cur = t & 1;
     // next step's input projection, in flight during the MFMAs
     float yr[4], yz[4], yn[4];
+    int tn[4];                          // TOK: P offset of step t + 2, or -1
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const bool ld = live[i] && t + 1 < T;
-      const float* p = gx + (ob[i] + (long)(t + 1) * H) * 3 - 2 * col;
-      yr[i] = ld ? p[0] : 0.f;
-      yz[i] = ld ? p[H] : 0.f;
-      yn[i] = ld ? p[2 * H] : 0.f;
+      if constexpr (TOK) {
+        // tk is -1 beyond the last step and on dead rows
+        const float* p = gx + tk[i] + col;
+        yr[i] = tk[i] >= 0 ? p[0] : 0.f;
+        yz[i] = tk[i] >= 0 ? p[H] : 0.f;
+        yn[i] = tk[i] >= 0 ? p[2 * H] : 0.f;
+        tn[i] = gru_tok_off(tok, (b0 + 4 * lk + i) * T + t + 2,
+                            live[i] && t + 2 < T, V, 3 * H);
+      } else {
+        const bool ld = live[i] && t + 1 < T;
+        const float* p = gx + (ob[i] + (long)(t + 1) * H) * 3 - 2 * col;
+        yr[i] = ld ? p[0] : 0.f;
+        yz[i] = ld ? p[H] : 0.f;
+        yn[i] = ld ? p[2 * H] : 0.f;
+      }
     }
     gru_f4 ar = {br, br, br, br}, az = {bz, bz, bz, bz},
            an = {bn, bn, bn, bn};
@@ -174,6 +195,7 @@ gru_fwd_reg_k(const float* __restrict__ gx, const void* __restrict__ w,
         }
       }
       xr[i] = yr[i]; xz[i] = yz[i]; xn[i] = yn[i];
+      if constexpr (TOK) tk[i] = tn[i];
     }
     __syncthreads();
   }

@@ -21,6 +21,7 @@
 #include "head.h"
 #include "gru.h"
 #include "gru_wide.h"
+#include "gru_tok.h"
 #include "linearround.h"
 #include "mlpround.h"
 #include "cnnround.h"
@@ -2509,12 +2510,12 @@ std::vector<torch::Tensor> gru_wide_fwd(torch::Tensor gx, torch::Tensor w_hh,
   const int bbf = b_hh.scalar_type() == torch::kBFloat16;
   const unsigned grid = (unsigned)((B + GRU_ROWS - 1) / GRU_ROWS);
 #define GRU_FWD_LAUNCH(NT)                                                   \
-  hipLaunchKernelGGL(gru_fwd_reg_k<NT>, dim3(grid), dim3(NT * WAVE), 0,      \
-                     STREAM, gx.data_ptr<float>(), w_hh.data_ptr(), wbf,     \
-                     b_hh.data_ptr(), bbf, h0.data_ptr<float>(),             \
-                     out.data_ptr<float>(),                                  \
+  hipLaunchKernelGGL((gru_fwd_reg_k<NT, false>), dim3(grid),                 \
+                     dim3(NT * WAVE), 0, STREAM, gx.data_ptr<float>(),       \
+                     w_hh.data_ptr(), wbf, b_hh.data_ptr(), bbf,             \
+                     h0.data_ptr<float>(), out.data_ptr<float>(),            \
                      save_gates ? gates.data_ptr<float>() : nullptr, (int)B, \
-                     (int)T, (int)H)
+                     (int)T, (int)H, (const long*)nullptr, 0)
   switch ((H + 15) / 16) {
     case 5: GRU_FWD_LAUNCH(5); break;
     case 6: GRU_FWD_LAUNCH(6); break;
@@ -2559,6 +2560,150 @@ std::vector<torch::Tensor> gru_wide_bwd(torch::Tensor dout, torch::Tensor out,
   }
 #undef GRU_BWD_LAUNCH
   return {dgx, dgh, dh0};
+}
+
+// --------------------------------------------------------------------------
+// token input: gx[b, t] = P[tok[b, t]] gathered inside the forward kernels
+// (gru.h / gru_wide.h, TOK variant) and the one-launch parameter-gradient
+// reduce (gru_tok.h).  tok is never read on the host: a token outside [0, V)
+// reads gx = 0 and adds nothing to dP (nn.Embedding faults on such a token).
+// --------------------------------------------------------------------------
+static void gru_check_tok(const char* who, const torch::Tensor& tok,
+                          const torch::Device& dev) {
+  TORCH_CHECK(tok.is_cuda() && tok.device() == dev, who,
+              ": tok must be on the same GPU");
+  TORCH_CHECK(tok.scalar_type() == torch::kLong, who, ": tok must be int64");
+  TORCH_CHECK(tok.dim() == 2 && tok.is_contiguous(), who,
+              ": tok must be contiguous [B, T], got ", tok.sizes());
+}
+
+static std::vector<torch::Tensor> gru_tok_fwd_any(
+    const char* who, bool wide, const torch::Tensor& P,
+    const torch::Tensor& tok, const torch::Tensor& w_hh,
+    const torch::Tensor& b_hh, const torch::Tensor& h0, bool save_gates) {
+  TORCH_CHECK(P.is_cuda() && P.dim() == 2 && P.is_contiguous(), who,
+              ": P must be contiguous [V, 3H] on GPU");
+  TORCH_CHECK(P.scalar_type() == torch::kFloat, who, ": P must be fp32");
+  TORCH_CHECK(P.size(1) % 3 == 0, who, ": P is ", P.sizes(),
+              ", expected [V, 3H]");
+  const long V = P.size(0), H = P.size(1) / 3;
+  TORCH_CHECK(V >= 1, who, ": empty table (V = 0)");
+  const auto dev = P.device();
+  gru_check_tok(who, tok, dev);
+  const long B = tok.size(0), T = tok.size(1);
+  if (wide)
+    gru_wide_check_dims(who, B, T, H);
+  else
+    gru_check_dims(who, B, T, H);
+  // the kernels keep table offsets and token indices in 32 bits
+  TORCH_CHECK(V * 3 * H < (1L << 31) && B * T < (1L << 31), who,
+              ": table or token tensor too large");
+  gru_check_param(who, "w_hh", w_hh, {3 * H, H}, dev);
+  gru_check_param(who, "b_hh", b_hh, {3 * H}, dev);
+  gru_check_f32(who, "h0", h0, {B, H}, dev);
+  auto out = torch::empty({B, T, H}, P.options());
+  auto gates = save_gates ? torch::empty({B, T, 4, H}, P.options())
+                          : torch::empty({0}, P.options());
+  const int wbf = w_hh.scalar_type() == torch::kBFloat16;
+  const int bbf = b_hh.scalar_type() == torch::kBFloat16;
+  const unsigned grid = (unsigned)((B + GRU_ROWS - 1) / GRU_ROWS);
+  float* gp = save_gates ? gates.data_ptr<float>() : nullptr;
+#define GRU_TOK_LAUNCH(NT)                                                   \
+  hipLaunchKernelGGL(gru_tok_fwd_k<NT>, dim3(grid), dim3(NT * WAVE), 0,      \
+                     STREAM, P.data_ptr<float>(), tok.data_ptr<long>(),      \
+                     (int)V, w_hh.data_ptr(), wbf, b_hh.data_ptr(), bbf,     \
+                     h0.data_ptr<float>(), out.data_ptr<float>(), gp,        \
+                     (int)B, (int)T, (int)H)
+#define GRU_TOK_WIDE_LAUNCH(NT)                                              \
+  hipLaunchKernelGGL((gru_fwd_reg_k<NT, true>), dim3(grid), dim3(NT * WAVE), \
+                     0, STREAM, P.data_ptr<float>(), w_hh.data_ptr(), wbf,   \
+                     b_hh.data_ptr(), bbf, h0.data_ptr<float>(),             \
+                     out.data_ptr<float>(), gp, (int)B, (int)T, (int)H,      \
+                     tok.data_ptr<long>(), (int)V)
+  switch ((H + 15) / 16) {
+    case 1: GRU_TOK_LAUNCH(1); break;
+    case 2: GRU_TOK_LAUNCH(2); break;
+    case 3: GRU_TOK_LAUNCH(3); break;
+    case 4: GRU_TOK_LAUNCH(4); break;
+    case 5: GRU_TOK_WIDE_LAUNCH(5); break;
+    case 6: GRU_TOK_WIDE_LAUNCH(6); break;
+    case 7: GRU_TOK_WIDE_LAUNCH(7); break;
+    default: GRU_TOK_WIDE_LAUNCH(8); break;
+  }
+#undef GRU_TOK_LAUNCH
+#undef GRU_TOK_WIDE_LAUNCH
+  return {out, gates};
+}
+
+// gru_fwd with gx[b, t] = P[tok[b, t]]: P [V, 3H] fp32, tok [B, T] int64,
+// 1 <= H <= 64; returns {out, gates} as gru_fwd
+std::vector<torch::Tensor> gru_tok_fwd(torch::Tensor P, torch::Tensor tok,
+                                       torch::Tensor w_hh, torch::Tensor b_hh,
+                                       torch::Tensor h0, bool save_gates) {
+  return gru_tok_fwd_any("gru_tok_fwd", false, P, tok, w_hh, b_hh, h0,
+                         save_gates);
+}
+
+// the same for 65 <= H <= 128 (gru_wide_fwd)
+std::vector<torch::Tensor> gru_tok_wide_fwd(torch::Tensor P,
+                                            torch::Tensor tok,
+                                            torch::Tensor w_hh,
+                                            torch::Tensor b_hh,
+                                            torch::Tensor h0,
+                                            bool save_gates) {
+  return gru_tok_fwd_any("gru_tok_wide_fwd", true, P, tok, w_hh, b_hh, h0,
+                         save_gates);
+}
+
+// waves per workgroup of gru_tok_grads_k when the caller names none: each wave
+// should get a few 4-row k-steps (measured: profiles/gru_notes.md)
+static int gru_tok_waves(long R) {
+  const long steps = (R + 3) / 4;
+  return steps >= 64 ? 16 : steps >= 16 ? 8 : 4;
+}
+
+// dgx, dgh [B, T, 3H], out [B, T, H], h0 [B, H] fp32, tok [B, T] int64 ->
+// {dP [V, 3H], dW_hh [3H, H], db_hh [3H]} fp32, one launch (gru_tok.h).
+// 1 <= H <= 128.  waves = 0: the built-in choice; 1..16 fixes the K split
+// (and with it the summation order) for measurements.
+std::vector<torch::Tensor> gru_tok_grads(torch::Tensor dgx, torch::Tensor dgh,
+                                         torch::Tensor out, torch::Tensor h0,
+                                         torch::Tensor tok, long V,
+                                         long waves) {
+  const char* who = "gru_tok_grads";
+  TORCH_CHECK(out.is_cuda() && out.dim() == 3 && out.is_contiguous(), who,
+              ": out must be contiguous [B, T, H] on GPU");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat, who, ": out must be fp32");
+  const long B = out.size(0), T = out.size(1), H = out.size(2);
+  TORCH_CHECK(H >= 1 && H <= GRU_WIDE_MAXH, who, ": unsupported H=", H,
+              " (1 <= H <= 128)");
+  TORCH_CHECK(B >= 1 && T >= 1, who, ": empty input");
+  TORCH_CHECK(V >= 1, who, ": empty table (V = 0)");
+  TORCH_CHECK(waves >= 0 && waves <= GRU_TOK_MAXW, who, ": waves is ", waves,
+              ", expected 0 .. 16");
+  const long MT = (3 * H + 15) / 16, NTH = (H + 15) / 16;
+  const long blocks = MT * NTH + (V + 15) / 16 * MT;
+  TORCH_CHECK(B < (1L << 31) && T < (1L << 31) && B * T < (1L << 31) &&
+                  V * 3 * H < (1L << 31) && blocks < (1L << 31), who,
+              ": input too large");
+  const auto dev = out.device();
+  gru_check_f32(who, "dgx", dgx, {B, T, 3 * H}, dev);
+  gru_check_f32(who, "dgh", dgh, {B, T, 3 * H}, dev);
+  gru_check_f32(who, "h0", h0, {B, H}, dev);
+  gru_check_tok(who, tok, dev);
+  TORCH_CHECK(tok.size(0) == B && tok.size(1) == T, who, ": tok is ",
+              tok.sizes(), ", expected [", B, ", ", T, "]");
+  auto dP = torch::empty({V, 3 * H}, out.options());
+  auto dW = torch::empty({3 * H, H}, out.options());
+  auto db = torch::empty({3 * H}, out.options());
+  const int nw = waves ? (int)waves : gru_tok_waves(B * T);
+  hipLaunchKernelGGL(gru_tok_grads_k, dim3((unsigned)blocks),
+                     dim3(nw * WAVE), 0, STREAM, dgx.data_ptr<float>(),
+                     dgh.data_ptr<float>(), out.data_ptr<float>(),
+                     h0.data_ptr<float>(), tok.data_ptr<long>(),
+                     dP.data_ptr<float>(), dW.data_ptr<float>(),
+                     db.data_ptr<float>(), B * T, (int)T, (int)H, (int)V);
+  return {dP, dW, db};
 }
 
 // ==========================================================================
@@ -3195,6 +3340,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_bwd", &gru_bwd);
   m.def("gru_wide_fwd", &gru_wide_fwd);
   m.def("gru_wide_bwd", &gru_wide_bwd);
+  m.def("gru_tok_fwd", &gru_tok_fwd);
+  m.def("gru_tok_wide_fwd", &gru_tok_wide_fwd);
+  m.def("gru_tok_grads", &gru_tok_grads, py::arg("dgx"), py::arg("dgh"),
+        py::arg("out"), py::arg("h0"), py::arg("tok"), py::arg("V"),
+        py::arg("waves") = 0);
   m.def("head_fwd", &head_fwd);
   m.def("head_bwd", &head_bwd);
   m.def("ce_topk_accum", &ce_topk_accum);

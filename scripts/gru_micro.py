@@ -13,6 +13,18 @@ Needs a GPU.
 (c) kernel launches per call of (a) and per step of (b), counted with the
     torch profiler (device-kernel events; memcpy / memset listed apart).
 
+With --tokens 1 a third setting joins (b): "tokens", the fused path plus
+FEDTORCH_FUSED_GRU_TOKENS (gru_tok_fwd + gru_tok_grads over the [V, 3H]
+table, ops/gru.py::gru_tok_seq); its baseline is "fused", the path without
+the third flag, in the same run.  Two more tables are printed:
+
+(d) embedding + GRU layer, forward + backward (gradients of the embedding
+    weight, h0 and the four GRU parameters), B in {10, 128}: stock / fused /
+    tokens.
+(e) gru_tok_grads alone against the cat + GEMM + sum it replaces
+    (hh_weight_grad + hh_bias_grad; the library side gets no dP), B in
+    {10, 128}, for 4, 8 and 16 waves per workgroup and the built-in choice.
+
 All settings are warmed up first, then sampled alternately in ONE process:
 each sample is device events around --iters repetitions, --samples samples
 per setting; min / median / max are printed so the spread is visible."""
@@ -31,7 +43,8 @@ from fedtorch_amd.components.models.rnn import CharGRU  # noqa: E402
 from fedtorch_amd.ops import gru as fgru  # noqa: E402
 
 H, T, V = 50, 50, 86
-SETTINGS = (('stock', False), ('fused', True))
+# name -> (FUSED_GRU, FUSED_GRU_TOKENS); --tokens 1 appends 'tokens'
+SETTINGS = [('stock', (False, False)), ('fused', (True, False))]
 
 
 def timed(fn, iters):
@@ -47,18 +60,23 @@ def timed(fn, iters):
     return t0.elapsed_time(t1) / iters
 
 
-def report(tag, t):
+def report(tag, t, base=None):
+    """every setting against `base`, or (default) against the one before it:
+    fused against stock, tokens against fused"""
     for name in t:
         v = sorted(t[name])
         print('%s %-6s min %.4f median %.4f max %.4f ms (%d samples)' % (
             tag, name, v[0], statistics.median(v), v[-1], len(v)))
-    s, f = t['stock'], t['fused']
-    print('%s fused range [%.4f, %.4f] vs stock [%.4f, %.4f]: %s; '
-          'median ratio stock/fused %.2f' % (
-              tag, min(f), max(f), min(s), max(s),
-              'disjoint, below' if max(f) < min(s) else
-              'disjoint, above' if min(f) > max(s) else 'overlap',
-              statistics.median(s) / statistics.median(f)))
+    names = list(t)
+    for prev, name in zip(names, names[1:]):
+        ref = base or prev
+        s, f = t[ref], t[name]
+        print('%s %s range [%.4f, %.4f] vs %s [%.4f, %.4f]: %s; '
+              'median ratio %s/%s %.2f' % (
+                  tag, name, min(f), max(f), ref, min(s), max(s),
+                  'disjoint, below' if max(f) < min(s) else
+                  'disjoint, above' if min(f) > max(s) else 'overlap',
+                  ref, name, statistics.median(s) / statistics.median(f)))
 
 
 def launches(fn):
@@ -82,21 +100,24 @@ def launches(fn):
 
 
 def set_flags(flag, a):
-    fgru._GRU_ENABLED = flag
-    fgru._GRU_WIDE_ENABLED = flag and bool(a.wide)
+    fused, tokens = flag if isinstance(flag, tuple) else (flag, False)
+    fgru._GRU_ENABLED = fused
+    fgru._GRU_WIDE_ENABLED = fused and bool(a.wide)
+    fgru._GRU_TOK_ENABLED = tokens
 
 
-def compare(tag, call, a):
-    for _name, flag in SETTINGS:                 # warm up ALL first
+def compare(tag, call, a, settings=None, base=None):
+    settings = settings or SETTINGS[:2]
+    for _name, flag in settings:                 # warm up ALL first
         for _ in range(a.warmup):
             call(flag)
-    t = {name: [] for name, _f in SETTINGS}
+    t = {name: [] for name, _f in settings}
     for _ in range(a.samples):                   # alternate the settings
-        for name, flag in SETTINGS:
+        for name, flag in settings:
             t[name].append(timed(lambda: call(flag), a.iters))
-    report(tag, t)
+    report(tag, t, base)
     if a.launches:
-        for name, flag in SETTINGS:
+        for name, flag in settings:
             print('%s %-6s launches per call: kernels %s, memcpy/memset %s'
                   % ((tag, name) + launches(lambda: call(flag))))
 
@@ -138,7 +159,51 @@ def train_step(a):
         F.cross_entropy(m(x), y).backward()
         opt.step()
 
-    compare('CharGRU train step B=%d ms/step' % B, call, a)
+    compare('CharGRU train step B=%d ms/step' % B, call, a, SETTINGS)
+
+
+def embedding_layer(a):
+    """(d): nn.Embedding + GRU layer, forward + backward"""
+    H = a.hidden
+    for B in (10, 128):
+        torch.manual_seed(B)
+        enc = nn.Embedding(V, H).cuda()
+        gru = nn.GRU(H, H, batch_first=True).cuda()
+        tok = torch.randint(0, V, (B, T), device='cuda')
+        h0 = torch.randn(1, B, H, device='cuda', requires_grad=True)
+        dout = torch.randn(B, T, H, device='cuda')
+        leaves = (enc.weight, h0) + tuple(gru.parameters())
+
+        def call(flag):
+            set_flags(flag, a)
+            out, _hn = fgru.gru_tok_seq(enc, gru, tok, h0)
+            torch.autograd.grad(out, leaves, dout)
+
+        compare('embedding+layer fwd+bwd B=%d ms/call' % B, call, a,
+                SETTINGS)
+
+
+def reduce_alone(a):
+    """(e): gru_tok_grads against hh_weight_grad + hh_bias_grad"""
+    H = a.hidden
+    for B in (10, 128):
+        torch.manual_seed(B)
+        dgx = torch.randn(B, T, 3 * H, device='cuda')
+        dgh = torch.randn(B, T, 3 * H, device='cuda')
+        out = torch.randn(B, T, H, device='cuda')
+        h0 = torch.randn(B, H, device='cuda')
+        tok = torch.randint(0, V, (B, T), device='cuda')
+
+        def call(waves):
+            if waves is None:
+                fgru.hh_weight_grad(dgh, out, h0)
+                fgru.hh_bias_grad(dgh)
+            else:
+                ops._C.gru_tok_grads(dgx, dgh, out, h0, tok, V, waves)
+
+        compare('reduce alone B=%d ms/call' % B, call, a,
+                [('library', None), ('w4', 4), ('w8', 8), ('w16', 16),
+                 ('auto', 0)], base='library')
 
 
 def main():
@@ -149,18 +214,26 @@ def main():
     ap.add_argument('--launches', type=int, default=1)
     ap.add_argument('--hidden', type=int, default=H)
     ap.add_argument('--wide', type=int, default=0)
+    ap.add_argument('--tokens', type=int, default=0)
     a = ap.parse_args()
+    if a.tokens:
+        SETTINGS.append(('tokens', (True, True)))
     if a.hidden > (fgru.MAX_H_WIDE if a.wide else fgru.MAX_H):
         raise SystemExit('H = %d is the library path either way (--wide 1 '
                          'covers 65..128)' % a.hidden)
     if not (torch.cuda.is_available() and ops.hip_available()):
         raise SystemExit('gru_micro needs a GPU and the built kernel pack')
-    old = fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED
+    old = (fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED, fgru._GRU_TOK_ENABLED)
     try:
-        layer(a)
+        if a.tokens:
+            reduce_alone(a)
+            embedding_layer(a)
+        else:
+            layer(a)
         train_step(a)
     finally:
-        fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED = old
+        (fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED,
+         fgru._GRU_TOK_ENABLED) = old
     print('GRU_MICRO_OK')
 
 
