@@ -997,6 +997,255 @@ def cnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
 
 
 # --------------------------------------------------------------------------
+# packed char-GRU: all clients' local steps batched per layer
+# (hip/rnnround.h)
+# --------------------------------------------------------------------------
+
+# kept equal to the RNNROUND_MAX* of hip/rnnround.h (a GPU test compares)
+RNNROUND_MAXB = 64
+RNNROUND_MAXH = 64
+RNNROUND_MAXV = 128
+RNNROUND_MAXK = 128
+
+
+def rnn_round_limits():
+    """the largest B, H, V, K of ops.rnn_local_rounds"""
+    return dict(B=RNNROUND_MAXB, H=RNNROUND_MAXH, V=RNNROUND_MAXV,
+                K=RNNROUND_MAXK)
+
+
+def _rnn_layout_flat(layout):
+    """[enc_off, V, H, w_ih, w_hh, b_ih, b_hh, dec_w, dec_b, K] of a layout
+    dict"""
+    enc = tuple(int(v) for v in layout['encoder'])
+    dec = tuple(int(v) for v in layout['decoder'])
+    if len(enc) != 3 or len(dec) != 3:
+        raise ValueError('rnn_local_rounds: a layout is encoder=(off, V, H), '
+                         'w_ih / w_hh / b_ih / b_hh=off, decoder=(w_off, '
+                         'b_off, K)')
+    return list(enc) + [int(layout[k]) for k in
+                        ('w_ih', 'w_hh', 'b_ih', 'b_hh')] + list(dec)
+
+
+def rnn_layout_check(layout, N):
+    """the launcher's layout checks (ValueError); returns the spans
+    [(start, end)] of the seven parameter tensors in the arena, in the order
+    encoder, w_ih, w_hh, b_ih, b_hh, decoder w, b"""
+    who = 'rnn_local_rounds: '
+    enc, V, H, wih, whh, bih, bhh, dw, db, K = _rnn_layout_flat(layout)
+    if not 1 <= H <= RNNROUND_MAXH:
+        raise ValueError(who + 'unsupported H=%d (1 <= H <= %d)'
+                         % (H, RNNROUND_MAXH))
+    if not (1 <= V <= RNNROUND_MAXV and 1 <= K <= RNNROUND_MAXK):
+        raise ValueError(who + 'unsupported V=%d K=%d (1 <= V <= %d, 1 <= K '
+                         '<= %d)' % (V, K, RNNROUND_MAXV, RNNROUND_MAXK))
+    spans = [(enc, enc + V * H), (wih, wih + 3 * H * H),
+             (whh, whh + 3 * H * H), (bih, bih + 3 * H), (bhh, bhh + 3 * H),
+             (dw, dw + K * H), (db, db + K)]
+    for lo, hi in spans:
+        if lo < 0 or hi > N:
+            raise ValueError(who + 'layout tensor [%d, %d) does not fit the '
+                             'arena of %d' % (lo, hi, N))
+    order = sorted(spans)
+    for (_l0, h0), (l1, _h1) in zip(order, order[1:]):
+        if h0 > l1:
+            raise ValueError(who + 'layout tensors overlap at arena element '
+                             '%d' % l1)
+    return spans
+
+
+def rnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
+                     mom_init, snap, k_cut, hidden, hid_rows, *, layout,
+                     wd_numel, weight_decay, momentum, dampening, nesterov):
+    """All local SGD steps of a round, for every packed client of the
+    char-GRU of `components/models/rnn.py` (one layer, gate order r, z, n),
+    batched per layer.
+
+    X [M, T] int32 tokens, Y [M, T] int32 targets: a row is one window;
+    idx [C, S, B] int32 rows of X per sample, -1 = padding, the valid rows
+    of a step form a prefix, 1 <= B <= 64; steps, lr [C, S], server,
+    replicas, in_mom, mom_init, snap and k_cut exactly as in
+    `cnn_local_rounds`.  hidden [C, B, H] f32 and hid_rows [C] int32 (both
+    in/out) are every client's carried hidden state (`CharGRU.hidden`).
+
+    layout: dict(encoder=(off, V, H), w_ih=off, w_hh=off, b_ih=off,
+    b_hh=off, decoder=(w_off, b_off, K)): arena offsets of the seven
+    parameter tensors.  Limits: `rnn_round_limits()`.
+
+    for every client c with steps[c] > 0:
+      replicas[c] <- server                    (whole row, pad gaps included)
+      for s in 0 .. steps[c]-1, rows r = idx[c, s, :n], n >= 1:
+        [snap[c] <- replicas[c]   if s + 1 == k_cut]
+        h0 = hidden[c, :n] if hid_rows[c] == n else 0
+        P = E W_ih^T + b_ih ; gx[b, t] = P[X[r_b, t]], 0 (and no gradient)
+        for a token outside [0, V) ; out, h_T = GRU(gx, h0)
+        logits = out W_d^T + b_d ; loss[c, s] = mean CE over the n T
+        positions against Y[r] ; backward of exactly that ; the local branch
+        of `fused_sgd_step` (weight decay for arena index < wd_numel,
+        momentum / dampening / nesterov / first use), in place in
+        replicas[c] (and in_mom[c])
+        hidden[c, :n] <- h_T (detached) ; hid_rows[c] <- n
+      mom_init[c] <- 1 (with momentum)
+
+    Returns loss [C, S]: the mean loss of each executed step, 0 elsewhere.
+    The eager twin raises ValueError for valid rows that are no prefix and
+    for an executed step with no valid row; the HIP path cannot see a device
+    idx: it takes the valid prefix and stays in bounds and finite."""
+    dev = X.device
+    if in_mom is None:
+        in_mom = torch.empty(0, device=dev)
+    if snap is None:
+        snap = torch.empty(0, device=dev)
+    if _use_hip(X, server, replicas):
+        return _C.rnn_local_rounds(
+            X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap,
+            int(k_cut), hidden, hid_rows, _rnn_layout_flat(layout),
+            int(wd_numel), float(weight_decay), float(momentum),
+            float(dampening), bool(nesterov))
+
+    # eager twin: a per-client, per-step loop; the gradients come from
+    # autograd over F.embedding / F.linear / the GRU cell spelled out /
+    # F.cross_entropy, the update from the fused-SGD twin above over the
+    # whole row.  Pad gaps are put back afterwards.
+    import torch.nn.functional as Fn
+    who = 'rnn_local_rounds: '
+    for name, t, dt in (('X', X, torch.int32), ('Y', Y, torch.int32),
+                        ('idx', idx, torch.int32),
+                        ('steps', steps, torch.int32),
+                        ('lr', lr, torch.float32),
+                        ('server', server, torch.float32),
+                        ('replicas', replicas, torch.float32),
+                        ('mom_init', mom_init, torch.int32),
+                        ('hidden', hidden, torch.float32),
+                        ('hid_rows', hid_rows, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError(who + '%s must be contiguous %s on %s'
+                             % (name, dt, dev))
+    if X.dim() != 2 or idx.dim() != 3 or server.dim() != 1:
+        raise ValueError(who + 'X is [M, T], idx [C, S, B], server [N]')
+    C, S, B = idx.shape
+    N = server.numel()
+    M, T = X.shape
+    use_mom = momentum != 0
+    for name, t in (('in_mom', in_mom if use_mom else None),
+                    ('snap', snap if snap.numel() else None)):
+        if t is not None and (t.dtype != torch.float32
+                              or not t.is_contiguous() or t.device != dev):
+            raise ValueError(who + '%s must be contiguous %s on %s'
+                             % (name, torch.float32, dev))
+    if nesterov and (not use_mom or dampening != 0):
+        raise ValueError(who + 'nesterov needs a momentum and zero '
+                         'dampening')
+    spans = rnn_layout_check(layout, N)
+    _enc, V, H, _wih, _whh, _bih, _bhh, _dw, _db, K = \
+        _rnn_layout_flat(layout)
+    want = [('Y', Y, (M, T)), ('steps', steps, (C,)), ('lr', lr, (C, S)),
+            ('replicas', replicas, (C, N)), ('mom_init', mom_init, (C,)),
+            ('hidden', hidden, (C, B, H)), ('hid_rows', hid_rows, (C,))]
+    if use_mom:
+        want.append(('in_mom', in_mom, (C, N)))
+    if snap.numel():
+        want.append(('snap', snap, (C, N)))
+    for name, t, shp in want:
+        if tuple(t.shape) != shp:
+            raise ValueError(who + '%s must be %s, got %s'
+                             % (name, list(shp), list(t.shape)))
+    if not 1 <= B <= RNNROUND_MAXB:
+        raise ValueError(who + 'unsupported B=%d (1 <= B <= %d)'
+                         % (B, RNNROUND_MAXB))
+    if M < 1 or T < 1:
+        raise ValueError(who + 'empty X')
+    if k_cut < 0:
+        raise ValueError(who + 'k_cut is %d, expected >= 0' % k_cut)
+    if not 0 <= wd_numel <= N:
+        raise ValueError(who + 'wd_numel is %d, the arena has %d'
+                         % (wd_numel, N))
+    n_steps = steps.tolist()
+    if max(n_steps) > S:
+        raise ValueError(who + 'steps holds %d but idx has S=%d'
+                         % (max(n_steps), S))
+    if int(idx.max()) >= M:
+        raise ValueError(who + 'idx holds row %d but X has %d rows'
+                         % (int(idx.max()), M))
+    for c in range(C):
+        for s in range(n_steps[c]):
+            ok = idx[c, s] >= 0
+            n = int(ok.sum())
+            if n < 1:
+                raise ValueError(who + 'step %d of client %d has no sample'
+                                 % (s, c))
+            if not bool(ok[:n].all()):
+                raise ValueError(who + 'the valid rows of step %d of client '
+                                 '%d are not a prefix' % (s, c))
+    shapes = [(V, H), (3 * H, H), (3 * H, H), (3 * H,), (3 * H,), (K, H),
+              (K,)]
+    loss = torch.zeros((C, S), dtype=torch.float32, device=dev)
+    inits = mom_init.tolist()
+    rows_kept = hid_rows.tolist()
+    gap = torch.ones_like(server, dtype=torch.bool)
+    for lo, hi in spans:
+        gap[lo:hi] = False
+    for c in range(C):
+        if n_steps[c] <= 0:
+            continue
+        p = server.clone()
+        grad = torch.zeros_like(p)
+        mom_gaps = in_mom[c][gap].clone() if use_mom else None
+        for s in range(n_steps[c]):
+            if snap.numel() and s + 1 == k_cut:
+                snap[c].copy_(torch.where(gap, server, p))
+            rows = idx[c, s]
+            rows = rows[rows >= 0].long()
+            n = rows.numel()
+            ts = [p[lo:hi].clone().view(shp).requires_grad_(True)
+                  for (lo, hi), shp in zip(spans, shapes)]
+            E, w_ih, w_hh, b_ih, b_hh, w_d, b_d = ts
+            tok = X[rows].long()
+            known = (tok >= 0) & (tok < V)
+            h = hidden[c, :n].clone() if rows_kept[c] == n \
+                else torch.zeros((n, H), dtype=torch.float32, device=dev)
+            with torch.enable_grad():
+                emb = Fn.embedding(tok.clamp(0, V - 1), E)
+                gx = Fn.linear(emb, w_ih, b_ih) * known.unsqueeze(-1)
+                outs = []
+                for t in range(T):
+                    gh = Fn.linear(h, w_hh, b_hh)
+                    xr, xz, xn = gx[:, t].chunk(3, dim=1)
+                    hr, hz, hn = gh.chunk(3, dim=1)
+                    r = torch.sigmoid(xr + hr)
+                    z = torch.sigmoid(xz + hz)
+                    g = torch.tanh(xn + r * hn)
+                    h = (1 - z) * g + z * h
+                    outs.append(h)
+                logits = Fn.linear(torch.stack(outs, dim=1), w_d, b_d)
+                l = Fn.cross_entropy(logits.reshape(n * T, K),
+                                     Y[rows].long().reshape(-1))
+                gs = torch.autograd.grad(l, ts)
+            loss[c, s] = l.detach()
+            hidden[c, :n] = h.detach()
+            rows_kept[c] = n
+            grad.zero_()
+            for (lo, hi), gt in zip(spans, gs):
+                grad[lo:hi].copy_(gt.reshape(-1))
+            fused_sgd_step(
+                p, grad, lr=float(lr[c, s]), scale=1.0,
+                weight_decay=weight_decay, in_momentum=momentum,
+                out_momentum=0.0, dampening=dampening, nesterov=nesterov,
+                apply_lr=True, apply_in_momentum=use_mom,
+                apply_out_momentum=False,
+                in_buf=in_mom[c] if use_mom else None,
+                first_in=use_mom and not inits[c], wd_numel=wd_numel)
+            if use_mom:
+                inits[c] = 1
+        replicas[c].copy_(torch.where(gap, server, p))
+        hid_rows[c] = rows_kept[c]
+        if use_mom:
+            in_mom[c][gap] = mom_gaps
+            mom_init[c] = 1
+    return loss
+
+
+# --------------------------------------------------------------------------
 # small host-side math (not perf-critical)
 # --------------------------------------------------------------------------
 

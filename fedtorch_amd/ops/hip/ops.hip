@@ -25,6 +25,7 @@
 #include "linearround.h"
 #include "mlpround.h"
 #include "cnnround.h"
+#include "rnnround.h"
 
 #define CHK(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
 #define STREAM at::hip::getCurrentHIPStream().stream()
@@ -3326,7 +3327,221 @@ torch::Tensor cnn_local_rounds(
   return loss;
 }
 
+// ==========================================================================
+// packed char-GRU: all clients' local steps batched per layer (rnnround.h)
+// ==========================================================================
+// [max B, max H, max V, max K]
+std::vector<int64_t> rnn_round_limits() {
+  return {RNNROUND_MAXB, RNNROUND_MAXH, RNNROUND_MAXV, RNNROUND_MAXV};
+}
+
+template <int NT>
+static void rnn_seq_launch(bool fwd, dim3 grid, hipStream_t st,
+                           const RnnRoundArgs& a, int s) {
+  if (fwd)
+    hipLaunchKernelGGL(rnn_gru_fwd_k<NT>, grid, dim3(NT * WAVE), 0, st, a, s);
+  else
+    hipLaunchKernelGGL(rnn_gru_bwd_k<NT>, grid, dim3(NT * WAVE), 0, st, a, s);
+}
+
+// layout: [enc_off, V, H, w_ih, w_hh, b_ih, b_hh, dec_w, dec_b, K] -- arena
+// offsets and shapes of the seven CharGRU tensors.  X, Y [M, T] int32 tokens
+// and targets; hidden [C, B, H] / hid_rows [C]: the clients' carried state
+// (in/out).  Returns loss [C, steps]; writes replicas / in_mom / mom_init /
+// snap / hidden / hid_rows of the clients with steps > 0.  idx and steps are
+// range-checked on the host unless the stream is capturing (the kernels never
+// address a row outside [0, M)).
+torch::Tensor rnn_local_rounds(
+    torch::Tensor X, torch::Tensor Y, torch::Tensor idx, torch::Tensor steps,
+    torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,
+    torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,
+    long k_cut, torch::Tensor hidden, torch::Tensor hid_rows,
+    std::vector<int64_t> layout, long wd_numel, double weight_decay,
+    double momentum, double dampening, bool nesterov) {
+  const char* who = "rnn_local_rounds";
+  TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous(), who,
+              ": X must be contiguous [M, T] on GPU");
+  TORCH_CHECK(X.scalar_type() == torch::kInt, who, ": X must be int32");
+  const long M = X.size(0), Tq = X.size(1);
+  const auto dev = X.device();
+  TORCH_CHECK(M >= 1 && Tq >= 1, who, ": empty X");
+  TORCH_CHECK(M * Tq < (1L << 31), who, ": X too large");
+  TORCH_CHECK(server.dim() == 1 && server.size(0) < (1L << 28), who,
+              ": server must be [N], N < 2^28");
+  TORCH_CHECK(server.scalar_type() == torch::kFloat, who,
+              ": fp32 arena only");
+  const long N = server.size(0);
+  linround_check(who, "Y", Y, torch::kInt, {M, Tq}, dev);
+  TORCH_CHECK(idx.dim() == 3, who, ": idx must be [C, S, B], got ",
+              idx.sizes());
+  const long C = idx.size(0), S = idx.size(1), B = idx.size(2);
+  TORCH_CHECK(C >= 1 && S >= 1, who, ": empty idx");
+  TORCH_CHECK(C < 65536 && S < (1L << 31), who, ": idx too large");
+  TORCH_CHECK(B >= 1 && B <= RNNROUND_MAXB, who, ": unsupported B=", B,
+              " (1 <= B <= ", RNNROUND_MAXB, ")");
+  linround_check(who, "idx", idx, torch::kInt, {C, S, B}, dev);
+  linround_check(who, "steps", steps, torch::kInt, {C}, dev);
+  linround_check(who, "lr", lr, torch::kFloat, {C, S}, dev);
+  linround_check(who, "server", server, torch::kFloat, {N}, dev);
+  linround_check(who, "replicas", replicas, torch::kFloat, {C, N}, dev);
+  linround_check(who, "mom_init", mom_init, torch::kInt, {C}, dev);
+  const bool use_mom = momentum != 0.0;
+  if (use_mom)
+    linround_check(who, "in_mom", in_mom, torch::kFloat, {C, N}, dev);
+  const bool has_snap = snap.numel() != 0;
+  if (has_snap) linround_check(who, "snap", snap, torch::kFloat, {C, N}, dev);
+  TORCH_CHECK(k_cut >= 0, who, ": k_cut is ", k_cut, ", expected >= 0");
+  TORCH_CHECK(!nesterov || (use_mom && dampening == 0.0), who,
+              ": nesterov needs a momentum and zero dampening");
+  TORCH_CHECK(wd_numel >= 0 && wd_numel <= N, who, ": wd_numel is ", wd_numel,
+              ", the arena has ", N);
+
+  // the layout
+  TORCH_CHECK(layout.size() == 10, who, ": layout must hold 10 numbers "
+              "(encoder off, V, H, w_ih, w_hh, b_ih, b_hh, decoder w, b, K), "
+              "got ", layout.size());
+  const long V = layout[1], H = layout[2], K = layout[9];
+  TORCH_CHECK(H >= 1 && H <= RNNROUND_MAXH, who, ": unsupported H=", H,
+              " (1 <= H <= ", RNNROUND_MAXH, ")");
+  TORCH_CHECK(V >= 1 && V <= RNNROUND_MAXV && K >= 1 && K <= RNNROUND_MAXV,
+              who, ": unsupported V=", V, " K=", K, " (1 <= V, K <= ",
+              RNNROUND_MAXV, ")");
+  linround_check(who, "hidden", hidden, torch::kFloat, {C, B, H}, dev);
+  linround_check(who, "hid_rows", hid_rows, torch::kInt, {C}, dev);
+  RnnLayout lay;
+  lay.V = (int)V; lay.H = (int)H; lay.K = (int)K;
+  const long offs[RNN_NTENS] = {layout[0], layout[3], layout[4], layout[5],
+                                layout[6], layout[7], layout[8]};
+  const long lens[RNN_NTENS] = {V * H, 3 * H * H, 3 * H * H, 3 * H, 3 * H,
+                                K * H, K};
+  const char* names[RNN_NTENS] = {"encoder", "w_ih", "w_hh", "b_ih", "b_hh",
+                                  "decoder weight", "decoder bias"};
+  std::vector<std::pair<long, long>> spans;      // [start, end) in the arena
+  lay.start[0] = 0;
+  for (int q = 0; q < RNN_NTENS; ++q) {
+    TORCH_CHECK(offs[q] >= 0 && offs[q] + lens[q] <= N, who, ": layout ",
+                names[q], " [", offs[q], ", +", lens[q],
+                ") does not fit the arena of ", N);
+    spans.emplace_back(offs[q], offs[q] + lens[q]);
+    lay.off[q] = (int)offs[q];
+    lay.start[q + 1] = lay.start[q] + (int)lens[q];
+  }
+  std::sort(spans.begin(), spans.end());
+  for (size_t i = 1; i < spans.size(); ++i)
+    TORCH_CHECK(spans[i - 1].second <= spans[i].first, who,
+                ": layout tensors overlap at arena element ", spans[i].first);
+
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(STREAM, &cap) == hipSuccess, who,
+              ": hipStreamIsCapturing failed");
+  if (cap == hipStreamCaptureStatusNone) {
+    const long top = idx.max().item<int>();
+    TORCH_CHECK(top < M, who, ": idx holds row ", top, " but X has ", M,
+                " rows");
+    const long most = steps.max().item<int>();
+    TORCH_CHECK(most <= S, who, ": steps holds ", most, " but idx has S=", S);
+  }
+
+  // workspace per client
+  const long BT = B * Tq, ltiles = (BT + 15) / 16;
+  long off = 0;
+  lay.P = (int)off;     off += V * 3 * H;
+  lay.dP = (int)off;    off += V * 3 * H;
+  lay.h0 = (int)off;    off += B * H;
+  lay.lossp = (int)off; off += ltiles;
+  lay.grad = (int)off;  off += N;
+  TORCH_CHECK(off + BT * (12 * H + K) < (1L << 30), who,
+              ": B*T=", BT, " needs too large a workspace");
+  lay.out = (int)off;   off += BT * H;
+  lay.dout = (int)off;  off += BT * H;
+  lay.gates = (int)off; off += BT * 4 * H;
+  lay.dgx = (int)off;   off += BT * 3 * H;
+  lay.dgh = (int)off;   off += BT * 3 * H;
+  lay.dl = (int)off;    off += BT * K;
+  lay.ws_stride = off;
+  auto ws = torch::empty({C, off}, server.options());
+  auto tokw = torch::empty({C, BT}, X.options());
+  auto loss = torch::zeros({C, S}, server.options());
+
+  RnnRoundArgs a;
+  MlpRoundArgs& m = a.m;
+  m.X = nullptr;
+  m.Y = nullptr;
+  m.idx = idx.data_ptr<int>();
+  m.steps = steps.data_ptr<int>();
+  m.lr = lr.data_ptr<float>();
+  m.server = server.data_ptr<float>();
+  m.replicas = replicas.data_ptr<float>();
+  m.in_mom = use_mom ? in_mom.data_ptr<float>() : nullptr;
+  m.mom_init = mom_init.data_ptr<int>();
+  m.snap = has_snap ? snap.data_ptr<float>() : nullptr;
+  m.loss = loss.data_ptr<float>();
+  m.ws = ws.data_ptr<float>();
+  m.corr_rows = nullptr; m.ctrl_s = nullptr; m.prox_mu = 0.f; m.corr = 0;
+  m.M = (int)M; m.B = (int)B; m.T = (int)S; m.N = (int)N;
+  m.k_cut = (int)std::min<long>(k_cut, 1L << 30);
+  m.use_mom = use_mom; m.nesterov = nesterov; m.wd_numel = (int)wd_numel;
+  m.wd = (float)weight_decay; m.mom = (float)momentum;
+  m.omd = (float)(1.0 - dampening); m.eps = 0.f;
+  m.lay = MlpLayout{};
+  a.tok = X.data_ptr<int>();
+  a.tgt = Y.data_ptr<int>();
+  a.hidden = hidden.data_ptr<float>();
+  a.hid_rows = hid_rows.data_ptr<int>();
+  a.tokw = tokw.data_ptr<int>();
+  a.Tq = (int)Tq;
+  a.lay = lay;
+
+  const dim3 blk(RNNROUND_THREADS), blkr(RNN_NW * WAVE);
+  const unsigned Cu = (unsigned)C;
+  const unsigned rowb =
+      (unsigned)std::min<long>((N + 4 * MLPROUND_THREADS - 1) /
+                                   (4 * MLPROUND_THREADS), 64);
+  auto t16 = [](long n) { return (n + 15) / 16; };
+  const long wpb = RNNROUND_THREADS / WAVE;
+  const long NHT = t16(H), N3T = t16(3 * H), NVT = t16(V), NKT = t16(K);
+  const dim3 g_tab((unsigned)((NVT * N3T + wpb - 1) / wpb), Cu);
+  const dim3 g_seq((unsigned)t16(B), Cu);
+  const dim3 g_dec((unsigned)ltiles, Cu);
+  const dim3 g_decb(
+      (unsigned)(NKT * NHT + (ltiles * NHT + RNN_NW - 1) / RNN_NW), Cu);
+  const dim3 g_grads((unsigned)(N3T * NHT + NVT * N3T), Cu);
+  const dim3 g_tabb((unsigned)(((NVT + N3T) * NHT + wpb - 1) / wpb), Cu);
+  const dim3 g_upd(
+      (unsigned)std::min<long>((lay.start[RNN_NTENS] + 4 * RNNROUND_THREADS -
+                                1) / (4 * RNNROUND_THREADS), 64), Cu);
+  auto seq = [&](bool fwd, int s) {
+    switch ((int)NHT) {
+      case 1: rnn_seq_launch<1>(fwd, g_seq, STREAM, a, s); break;
+      case 2: rnn_seq_launch<2>(fwd, g_seq, STREAM, a, s); break;
+      case 3: rnn_seq_launch<3>(fwd, g_seq, STREAM, a, s); break;
+      default: rnn_seq_launch<4>(fwd, g_seq, STREAM, a, s); break;
+    }
+  };
+  hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, rowb), dim3(MLPROUND_THREADS), 0,
+                     STREAM, m, 0);
+  for (int s = 0; s < (int)S; ++s) {
+    if (has_snap && s + 1 == k_cut)
+      hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, rowb), dim3(MLPROUND_THREADS),
+                         0, STREAM, m, 1);
+    hipLaunchKernelGGL(rnn_table_k, g_tab, blk, 0, STREAM, a, s);
+    seq(true, s);
+    hipLaunchKernelGGL(rnn_dec_k, g_dec, blk, 0, STREAM, a, s);
+    hipLaunchKernelGGL(rnn_dec_bwd_k, g_decb, blkr, 0, STREAM, a, s);
+    seq(false, s);
+    hipLaunchKernelGGL(rnn_grads_k, g_grads, blkr, 0, STREAM, a, s);
+    hipLaunchKernelGGL(rnn_table_bwd_k, g_tabb, blk, 0, STREAM, a, s);
+    hipLaunchKernelGGL(rnn_update_k, g_upd, blk, 0, STREAM, a, s);
+  }
+  if (use_mom)
+    hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, 1), dim3(MLPROUND_THREADS), 0,
+                       STREAM, m, 2);
+  return loss;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("rnn_local_rounds", &rnn_local_rounds);
+  m.def("rnn_round_limits", &rnn_round_limits);
   m.def("cnn_local_rounds", &cnn_local_rounds);
   m.def("cnn_round_limits", &cnn_round_limits);
   m.def("mlp_local_rounds", &mlp_local_rounds);

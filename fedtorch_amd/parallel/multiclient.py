@@ -61,6 +61,15 @@ _BATCHED_CNN_ENABLED = \
 _BATCHED_CNN_CORR_ENABLED = \
     os.environ.get('FEDTORCH_PACKED_BATCHED_CNN_CORR', '0') == '1'
 
+# Packed char-GRU clients (`rnn`): the local steps of all online clients
+# batched per layer (ops.rnn_local_rounds, hip/rnnround.h), fedavg (and DRFA
+# over it) only.  Every client carries its own hidden state there, as W x C
+# one-client ranks do; the slot loop threads the shared module's single
+# `hidden` through the clients.  Its own opt-in:
+# ``FEDTORCH_PACKED_BATCHED_RNN=1``; timings in profiles/packed_rnn_notes.md.
+_BATCHED_RNN_ENABLED = \
+    os.environ.get('FEDTORCH_PACKED_BATCHED_RNN', '0') == '1'
+
 
 class VirtualGraph(object):
     """graph facade so the dataset pipeline partitions over W*C clients."""
@@ -114,6 +123,8 @@ class ClientPack(object):
         self.train_loaders = [None] * self.C
         self.partial = torch.zeros(n, device=dev)
         self._stacked = None  # (X, Y, row offsets), see stacked_data()
+        self.hidden = None    # batched char-GRU rounds, see rnn_state()
+        self.hid_rows = None
         # per-client BatchNorm running stats (the reference's centered mode
         # gives every ClientCentered its own module and therefore its own
         # BN buffers; the shared compute module must swap them per client)
@@ -452,15 +463,111 @@ class ClientPack(object):
     def cnn_batched_eligible(self):
         return not self.cnn_batched_blockers()
 
-    def stacked_data(self):
+    # ---- batched round of the char-GRU (trainings/packed.py) ---------------
+    def rnn_layout(self):
+        """The layout ops.rnn_local_rounds takes -- dict(encoder=(off, V, H),
+        w_ih / w_hh / b_ih / b_hh=off, decoder=(w_off, b_off, K)) -- of the
+        compute module in the arena, or None when the module is not exactly
+        the one-layer CharGRU (input size = H) whose seven parameters are
+        exactly the arena's."""
+        from fedtorch_amd.components.models.rnn import CharGRU
+        model, arena = self.base.model, self.base.arena
+        if type(model) is not CharGRU or model.n_layers != 1:
+            return None
+        names = ['encoder.weight', 'gru.weight_ih_l0', 'gru.weight_hh_l0',
+                 'gru.bias_ih_l0', 'gru.bias_hh_l0', 'decoder.weight',
+                 'decoder.bias']
+        if sorted(arena.names) != sorted(names):
+            return None
+        gru, H = model.gru, model.hidden_size
+        if gru.input_size != H or gru.hidden_size != H or gru.bidirectional \
+                or not gru.batch_first or gru.dropout != 0 \
+                or model.encoder.embedding_dim != H \
+                or model.encoder.padding_idx is not None \
+                or model.encoder.max_norm is not None \
+                or model.decoder.in_features != H:
+            return None
+        off = lambda n: arena.offsets[arena.names.index(n)]  # noqa: E731
+        return dict(
+            encoder=(off(names[0]), int(model.encoder.num_embeddings), int(H)),
+            w_ih=off(names[1]), w_hh=off(names[2]), b_ih=off(names[3]),
+            b_hh=off(names[4]),
+            decoder=(off(names[5]), off(names[6]),
+                     int(model.decoder.out_features)))
+
+    def rnn_batched_blockers(self):
+        """Why this pack's rounds cannot run through ops.rnn_local_rounds: a
+        list of reasons, empty when they can."""
+        from fedtorch_amd.components.datasets.device_cache import \
+            DeviceCachedLoader
+        why = []
+        if not _BATCHED_RNN_ENABLED:
+            why.append('FEDTORCH_PACKED_BATCHED_RNN is not set')
+        layout = self.rnn_layout()
+        if layout is None:
+            why.append('model is not the one-layer char-GRU that fills the '
+                       'arena')
+        else:
+            try:
+                ops.rnn_layout_check(layout, self.base.arena.numel)
+            except ValueError as e:
+                why.append(str(e))
+        why += self._run_blockers(
+            getattr(self.args, 'federated_type', None) == 'fedavg')
+        loaders = self.train_loaders
+        if not all(isinstance(l, DeviceCachedLoader) and not l._aug
+                   for l in loaders):
+            why.append('a local loader is not an un-augmented '
+                       'DeviceCachedLoader')
+            return why
+        B = loaders[0].batch_size
+        if any(l.batch_size != B for l in loaders):
+            why.append('batch sizes differ between clients')
+        elif not 1 <= B <= ops.RNNROUND_MAXB:
+            why.append('batch size %d outside 1 .. %d'
+                       % (B, ops.RNNROUND_MAXB))
+        # the slot loop's `break` on a 1-sample batch is not reproduced
+        if any(not l.drop_last and len(l.x) % l.batch_size == 1
+               for l in loaders):
+            why.append('a partition leaves a 1-sample last batch')
+        if any(l.x.dim() != 2 or l.x.shape != l.y.shape
+               or l.x.is_floating_point() or l.y.is_floating_point()
+               or l.x.shape[1] != loaders[0].x.shape[1] for l in loaders):
+            why.append('loader rows are not integer windows of one length')
+        return why
+
+    def rnn_batched_eligible(self):
+        return not self.rnn_batched_blockers()
+
+    def rnn_state(self):
+        """(hidden [C, B, H] fp32, hid_rows [C] int32): every client's
+        carried hidden state of the batched char-GRU rounds (what
+        `CharGRU.hidden` is to a one-client rank).  Allocated on first use:
+        zeros, and no rows kept."""
+        if self.hidden is None:
+            dev = self.replicas.device
+            B = self.train_loaders[0].batch_size
+            H = self.base.model.hidden_size
+            self.hidden = torch.zeros((self.C, B, H), device=dev)
+            self.hid_rows = torch.zeros(self.C, dtype=torch.int32,
+                                        device=dev)
+        return self.hidden, self.hid_rows
+
+    def stacked_data(self, rnn=False):
         """(X [M, F] fp32, Y [M] int32 labels | fp32 targets, offsets [C+1]):
         the clients' cached partitions stacked; client j's rows are
-        offsets[j] .. offsets[j+1].  Built once, on first use."""
+        offsets[j] .. offsets[j+1].  Built once, on first use.  `rnn`: X and
+        Y are the int32 [M, T] token and target windows."""
         if self._stacked is None:
             from fedtorch_amd.components.models.convex import LeastSquare
             regress = isinstance(self.base.model, LeastSquare)
             xs, ys, offs = [], [], [0]
             for l in self.train_loaders:
+                if rnn:
+                    xs.append(l.x.to(torch.int32))
+                    ys.append(l.y.to(torch.int32))
+                    offs.append(offs[-1] + len(l.x))
+                    continue
                 xs.append(l.x.reshape(len(l.x), -1).float())
                 ys.append(l.y.reshape(-1).float() if regress
                           else l.y.reshape(-1).to(torch.int32))

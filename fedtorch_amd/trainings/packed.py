@@ -141,7 +141,7 @@ def _plan_local_rounds(client, pack, online):
 
 
 def _batched_local_rounds(client, pack, server, online, snap, k_cut,
-                          mlp=False, cnn=False):
+                          mlp=False, cnn=False, rnn=False):
     """The local steps of ALL online local clients in one batched op call:
     ops.linear_local_rounds for a linear model (FEDTORCH_PACKED_BATCHED,
     `ClientPack.batched_eligible`), ops.mlp_local_rounds for an MLP
@@ -149,14 +149,18 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
     `ClientPack.mlp_batched_eligible`), ops.cnn_local_rounds for the
     LeNet-style CNN (`cnn=True`: FEDTORCH_PACKED_BATCHED_CNN,
     `ClientPack.cnn_batched_eligible`); each with the gradient correction of
-    the federated type (`ClientPack.batched_correction`).
+    the federated type (`ClientPack.batched_correction`); and
+    ops.rnn_local_rounds for the char-GRU (`rnn=True`:
+    FEDTORCH_PACKED_BATCHED_RNN, `ClientPack.rnn_batched_eligible`, fedavg
+    only), with every client's own carried hidden state
+    (`ClientPack.rnn_state`).
 
     The host first walks the counters (`_plan_local_rounds`).  `snap`:
     DRFA's [C, N] snapshot arena, row j receives client j's parameters before
     its step `k_cut`.  Returns (loss [C, T], steps per client, lr of each
     client's last step)."""
     args = client.args
-    _X, _Y, _offs = pack.stacked_data()
+    _X, _Y, _offs = pack.stacked_data(rnn=rnn)
     plan, idx, lr, steps = _plan_local_rounds(client, pack, online)
     g = client.optimizer.param_groups[0]
     momentum = g['in_momentum'] if args.in_momentum else 0.0
@@ -169,7 +173,11 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
     sgd = dict(weight_decay=g['weight_decay'], momentum=momentum,
                dampening=g['dampening'], nesterov=g['nesterov'])
     corr = pack.batched_correction()
-    if cnn:
+    if rnn:
+        loss = ops.rnn_local_rounds(
+            *operands, *pack.rnn_state(), layout=pack.rnn_layout(),
+            wd_numel=client.arena.wd_numel, **sgd)
+    elif cnn:
         loss = ops.cnn_local_rounds(
             *operands, layout=pack.cnn_layout(),
             wd_numel=client.arena.wd_numel, **sgd, **corr)
@@ -238,13 +246,18 @@ def train_and_validate_federated_packed(client, pack, validate=False):
     # qualifies)
     batched_cnn = not batched and not batched_mlp \
         and pack.cnn_batched_eligible()
+    # char-GRU: likewise (off unless FEDTORCH_PACKED_BATCHED_RNN=1 and the
+    # pack qualifies); every client then carries its own hidden state
+    batched_rnn = not batched and not batched_mlp and not batched_cnn \
+        and pack.rnn_batched_eligible()
     log('packed local steps: {}'.format(
         'one batched launch per round' if batched
         else 'MLP layers batched over the clients' if batched_mlp
         else 'CNN layers batched over the clients' if batched_cnn
+        else 'char-GRU layers batched over the clients' if batched_rnn
         else 'slot loop'),
         args.debug)
-    batched = batched or batched_mlp or batched_cnn
+    batched = batched or batched_mlp or batched_cnn or batched_rnn
     run_client = (lambda j, server_flat, fn: None) if batched \
         else pack.run_client
     if ftype == 'scaffold':
@@ -323,7 +336,8 @@ def train_and_validate_federated_packed(client, pack, validate=False):
         if batched:
             _loss, taus, lrs = _batched_local_rounds(
                 client, pack, server, online, kth if drfa else None,
-                k_cut if drfa else 0, mlp=batched_mlp, cnn=batched_cnn)
+                k_cut if drfa else 0, mlp=batched_mlp, cnn=batched_cnn,
+                rnn=batched_rnn)
 
         partial = pack.accumulate_partial(server, weights)
         if ftype == 'scaffold':
