@@ -1014,6 +1014,18 @@ def rnn_round_limits():
                 K=RNNROUND_MAXK)
 
 
+# kept equal to RNNROUND_WIDE_MINH / _MAXH of hip/rnnround_wide.h
+RNNROUND_WIDE_MINH = 65
+RNNROUND_WIDE_MAXH = 128
+
+
+def rnn_wide_round_limits():
+    """the largest B, the H range and the largest V, K of
+    ops.rnn_wide_local_rounds"""
+    return dict(B=RNNROUND_MAXB, Hmin=RNNROUND_WIDE_MINH,
+                Hmax=RNNROUND_WIDE_MAXH, V=RNNROUND_MAXV, K=RNNROUND_MAXK)
+
+
 def _rnn_layout_flat(layout):
     """[enc_off, V, H, w_ih, w_hh, b_ih, b_hh, dec_w, dec_b, K] of a layout
     dict"""
@@ -1027,15 +1039,24 @@ def _rnn_layout_flat(layout):
                         ('w_ih', 'w_hh', 'b_ih', 'b_hh')] + list(dec)
 
 
-def rnn_layout_check(layout, N):
+def _rnn_who(wide):
+    """(name, smallest H, largest H) of the narrow / wide op"""
+    if wide:
+        return ('rnn_wide_local_rounds: ', RNNROUND_WIDE_MINH,
+                RNNROUND_WIDE_MAXH)
+    return 'rnn_local_rounds: ', 1, RNNROUND_MAXH
+
+
+def rnn_layout_check(layout, N, wide=False):
     """the launcher's layout checks (ValueError); returns the spans
     [(start, end)] of the seven parameter tensors in the arena, in the order
-    encoder, w_ih, w_hh, b_ih, b_hh, decoder w, b"""
-    who = 'rnn_local_rounds: '
+    encoder, w_ih, w_hh, b_ih, b_hh, decoder w, b.  `wide`: against the H
+    range of `rnn_wide_local_rounds`."""
+    who, hmin, hmax = _rnn_who(wide)
     enc, V, H, wih, whh, bih, bhh, dw, db, K = _rnn_layout_flat(layout)
-    if not 1 <= H <= RNNROUND_MAXH:
-        raise ValueError(who + 'unsupported H=%d (1 <= H <= %d)'
-                         % (H, RNNROUND_MAXH))
+    if not hmin <= H <= hmax:
+        raise ValueError(who + 'unsupported H=%d (%d <= H <= %d)'
+                         % (H, hmin, hmax))
     if not (1 <= V <= RNNROUND_MAXV and 1 <= K <= RNNROUND_MAXK):
         raise ValueError(who + 'unsupported V=%d K=%d (1 <= V <= %d, 1 <= K '
                          '<= %d)' % (V, K, RNNROUND_MAXV, RNNROUND_MAXK))
@@ -1091,13 +1112,36 @@ def rnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
     The eager twin raises ValueError for valid rows that are no prefix and
     for an executed step with no valid row; the HIP path cannot see a device
     idx: it takes the valid prefix and stays in bounds and finite."""
+    return _rnn_rounds(False, X, Y, idx, steps, lr, server, replicas, in_mom,
+                       mom_init, snap, k_cut, hidden, hid_rows, layout,
+                       wd_numel, weight_decay, momentum, dampening, nesterov)
+
+
+def rnn_wide_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
+                          mom_init, snap, k_cut, hidden, hid_rows, *, layout,
+                          wd_numel, weight_decay, momentum, dampening,
+                          nesterov):
+    """`rnn_local_rounds` for 65 <= H <= 128 (hip/rnnround_wide.h: the
+    sequence kernels keep their W_hh fragments in registers): the same
+    operands, contract and eager twin.  Limits: `rnn_wide_round_limits()`."""
+    return _rnn_rounds(True, X, Y, idx, steps, lr, server, replicas, in_mom,
+                       mom_init, snap, k_cut, hidden, hid_rows, layout,
+                       wd_numel, weight_decay, momentum, dampening, nesterov)
+
+
+def _rnn_rounds(wide, X, Y, idx, steps, lr, server, replicas, in_mom,
+                mom_init, snap, k_cut, hidden, hid_rows, layout, wd_numel,
+                weight_decay, momentum, dampening, nesterov):
+    """the body of `rnn_local_rounds` (1 <= H <= 64) and, `wide`, of
+    `rnn_wide_local_rounds` (65 <= H <= 128)"""
     dev = X.device
     if in_mom is None:
         in_mom = torch.empty(0, device=dev)
     if snap is None:
         snap = torch.empty(0, device=dev)
     if _use_hip(X, server, replicas):
-        return _C.rnn_local_rounds(
+        launch = _C.rnn_wide_local_rounds if wide else _C.rnn_local_rounds
+        return launch(
             X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap,
             int(k_cut), hidden, hid_rows, _rnn_layout_flat(layout),
             int(wd_numel), float(weight_decay), float(momentum),
@@ -1108,7 +1152,7 @@ def rnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
     # F.cross_entropy, the update from the fused-SGD twin above over the
     # whole row.  Pad gaps are put back afterwards.
     import torch.nn.functional as Fn
-    who = 'rnn_local_rounds: '
+    who = _rnn_who(wide)[0]
     for name, t, dt in (('X', X, torch.int32), ('Y', Y, torch.int32),
                         ('idx', idx, torch.int32),
                         ('steps', steps, torch.int32),
@@ -1136,7 +1180,7 @@ def rnn_local_rounds(X, Y, idx, steps, lr, server, replicas, in_mom,
     if nesterov and (not use_mom or dampening != 0):
         raise ValueError(who + 'nesterov needs a momentum and zero '
                          'dampening')
-    spans = rnn_layout_check(layout, N)
+    spans = rnn_layout_check(layout, N, wide)
     _enc, V, H, _wih, _whh, _bih, _bhh, _dw, _db, K = \
         _rnn_layout_flat(layout)
     want = [('Y', Y, (M, T)), ('steps', steps, (C,)), ('lr', lr, (C, S)),

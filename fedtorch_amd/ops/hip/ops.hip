@@ -26,6 +26,7 @@
 #include "mlpround.h"
 #include "cnnround.h"
 #include "rnnround.h"
+#include "rnnround_wide.h"
 
 #define CHK(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
 #define STREAM at::hip::getCurrentHIPStream().stream()
@@ -3334,14 +3335,29 @@ torch::Tensor cnn_local_rounds(
 std::vector<int64_t> rnn_round_limits() {
   return {RNNROUND_MAXB, RNNROUND_MAXH, RNNROUND_MAXV, RNNROUND_MAXV};
 }
+// 65 <= H <= 128 (rnnround_wide.h): [max B, min H, max H, max V, max K]
+std::vector<int64_t> rnn_wide_round_limits() {
+  return {RNNROUND_MAXB, RNNROUND_WIDE_MINH, RNNROUND_WIDE_MAXH,
+          RNNROUND_MAXV, RNNROUND_MAXV};
+}
 
+// the two sequence launches of a step: W_hh in LDS for NT <= 4, in registers
+// above
 template <int NT>
 static void rnn_seq_launch(bool fwd, dim3 grid, hipStream_t st,
                            const RnnRoundArgs& a, int s) {
-  if (fwd)
-    hipLaunchKernelGGL(rnn_gru_fwd_k<NT>, grid, dim3(NT * WAVE), 0, st, a, s);
-  else
-    hipLaunchKernelGGL(rnn_gru_bwd_k<NT>, grid, dim3(NT * WAVE), 0, st, a, s);
+  const dim3 blk(NT * WAVE);
+  if constexpr (NT <= 4) {
+    if (fwd)
+      hipLaunchKernelGGL(rnn_gru_fwd_k<NT>, grid, blk, 0, st, a, s);
+    else
+      hipLaunchKernelGGL(rnn_gru_bwd_k<NT>, grid, blk, 0, st, a, s);
+  } else {
+    if (fwd)
+      hipLaunchKernelGGL(rnn_gru_fwd_reg_k<NT>, grid, blk, 0, st, a, s);
+    else
+      hipLaunchKernelGGL(rnn_gru_bwd_reg_k<NT>, grid, blk, 0, st, a, s);
+  }
 }
 
 // layout: [enc_off, V, H, w_ih, w_hh, b_ih, b_hh, dec_w, dec_b, K] -- arena
@@ -3350,15 +3366,15 @@ static void rnn_seq_launch(bool fwd, dim3 grid, hipStream_t st,
 // (in/out).  Returns loss [C, steps]; writes replicas / in_mom / mom_init /
 // snap / hidden / hid_rows of the clients with steps > 0.  idx and steps are
 // range-checked on the host unless the stream is capturing (the kernels never
-// address a row outside [0, M)).
-torch::Tensor rnn_local_rounds(
-    torch::Tensor X, torch::Tensor Y, torch::Tensor idx, torch::Tensor steps,
-    torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,
-    torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,
-    long k_cut, torch::Tensor hidden, torch::Tensor hid_rows,
+// address a row outside [0, M)).  `who` accepts hmin <= H <= hmax.
+static torch::Tensor rnn_rounds(
+    const char* who, long hmin, long hmax, torch::Tensor X, torch::Tensor Y,
+    torch::Tensor idx, torch::Tensor steps, torch::Tensor lr,
+    torch::Tensor server, torch::Tensor replicas, torch::Tensor in_mom,
+    torch::Tensor mom_init, torch::Tensor snap, long k_cut,
+    torch::Tensor hidden, torch::Tensor hid_rows,
     std::vector<int64_t> layout, long wd_numel, double weight_decay,
     double momentum, double dampening, bool nesterov) {
-  const char* who = "rnn_local_rounds";
   TORCH_CHECK(X.is_cuda() && X.dim() == 2 && X.is_contiguous(), who,
               ": X must be contiguous [M, T] on GPU");
   TORCH_CHECK(X.scalar_type() == torch::kInt, who, ": X must be int32");
@@ -3401,8 +3417,8 @@ torch::Tensor rnn_local_rounds(
               "(encoder off, V, H, w_ih, w_hh, b_ih, b_hh, decoder w, b, K), "
               "got ", layout.size());
   const long V = layout[1], H = layout[2], K = layout[9];
-  TORCH_CHECK(H >= 1 && H <= RNNROUND_MAXH, who, ": unsupported H=", H,
-              " (1 <= H <= ", RNNROUND_MAXH, ")");
+  TORCH_CHECK(H >= hmin && H <= hmax, who, ": unsupported H=", H, " (", hmin,
+              " <= H <= ", hmax, ")");
   TORCH_CHECK(V >= 1 && V <= RNNROUND_MAXV && K >= 1 && K <= RNNROUND_MAXV,
               who, ": unsupported V=", V, " K=", K, " (1 <= V, K <= ",
               RNNROUND_MAXV, ")");
@@ -3515,7 +3531,11 @@ torch::Tensor rnn_local_rounds(
       case 1: rnn_seq_launch<1>(fwd, g_seq, STREAM, a, s); break;
       case 2: rnn_seq_launch<2>(fwd, g_seq, STREAM, a, s); break;
       case 3: rnn_seq_launch<3>(fwd, g_seq, STREAM, a, s); break;
-      default: rnn_seq_launch<4>(fwd, g_seq, STREAM, a, s); break;
+      case 4: rnn_seq_launch<4>(fwd, g_seq, STREAM, a, s); break;
+      case 5: rnn_seq_launch<5>(fwd, g_seq, STREAM, a, s); break;
+      case 6: rnn_seq_launch<6>(fwd, g_seq, STREAM, a, s); break;
+      case 7: rnn_seq_launch<7>(fwd, g_seq, STREAM, a, s); break;
+      default: rnn_seq_launch<8>(fwd, g_seq, STREAM, a, s); break;
     }
   };
   hipLaunchKernelGGL(mlp_rows_k, dim3(Cu, rowb), dim3(MLPROUND_THREADS), 0,
@@ -3539,9 +3559,35 @@ torch::Tensor rnn_local_rounds(
   return loss;
 }
 
+#define RNN_ROUNDS_PARAMS                                                    \
+  torch::Tensor X, torch::Tensor Y, torch::Tensor idx, torch::Tensor steps,  \
+      torch::Tensor lr, torch::Tensor server, torch::Tensor replicas,        \
+      torch::Tensor in_mom, torch::Tensor mom_init, torch::Tensor snap,      \
+      long k_cut, torch::Tensor hidden, torch::Tensor hid_rows,              \
+      std::vector<int64_t> layout, long wd_numel, double weight_decay,       \
+      double momentum, double dampening, bool nesterov
+#define RNN_ROUNDS_ARGS                                                      \
+  X, Y, idx, steps, lr, server, replicas, in_mom, mom_init, snap, k_cut,     \
+      hidden, hid_rows, layout, wd_numel, weight_decay, momentum, dampening, \
+      nesterov
+
+// 1 <= H <= 64: W_hh of the sequence kernels in LDS (rnnround.h)
+torch::Tensor rnn_local_rounds(RNN_ROUNDS_PARAMS) {
+  return rnn_rounds("rnn_local_rounds", 1, RNNROUND_MAXH, RNN_ROUNDS_ARGS);
+}
+
+// 65 <= H <= 128: W_hh fragments resident in registers (rnnround_wide.h); the
+// same operands, checks and launches otherwise
+torch::Tensor rnn_wide_local_rounds(RNN_ROUNDS_PARAMS) {
+  return rnn_rounds("rnn_wide_local_rounds", RNNROUND_WIDE_MINH,
+                    RNNROUND_WIDE_MAXH, RNN_ROUNDS_ARGS);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rnn_local_rounds", &rnn_local_rounds);
   m.def("rnn_round_limits", &rnn_round_limits);
+  m.def("rnn_wide_local_rounds", &rnn_wide_local_rounds);
+  m.def("rnn_wide_round_limits", &rnn_wide_round_limits);
   m.def("cnn_local_rounds", &cnn_local_rounds);
   m.def("cnn_round_limits", &cnn_round_limits);
   m.def("mlp_local_rounds", &mlp_local_rounds);

@@ -69,6 +69,11 @@ _BATCHED_CNN_CORR_ENABLED = \
 # ``FEDTORCH_PACKED_BATCHED_RNN=1``; timings in profiles/packed_rnn_notes.md.
 _BATCHED_RNN_ENABLED = \
     os.environ.get('FEDTORCH_PACKED_BATCHED_RNN', '0') == '1'
+# The same round for hidden sizes 65 .. 128 (ops.rnn_wide_local_rounds,
+# hip/rnnround_wide.h).  A second opt-in on top of the RNN one:
+# ``FEDTORCH_PACKED_BATCHED_RNN_WIDE=1``.
+_BATCHED_RNN_WIDE_ENABLED = \
+    os.environ.get('FEDTORCH_PACKED_BATCHED_RNN_WIDE', '0') == '1'
 
 
 class VirtualGraph(object):
@@ -495,9 +500,18 @@ class ClientPack(object):
             decoder=(off(names[5]), off(names[6]),
                      int(model.decoder.out_features)))
 
+    def rnn_batched_wide(self):
+        """True when the batched round of this pack is
+        ops.rnn_wide_local_rounds: FEDTORCH_PACKED_BATCHED_RNN_WIDE is set and
+        the char-GRU's hidden size is above ops.RNNROUND_MAXH."""
+        layout = self.rnn_layout()
+        return _BATCHED_RNN_WIDE_ENABLED and layout is not None \
+            and layout['encoder'][2] > ops.RNNROUND_MAXH
+
     def rnn_batched_blockers(self):
-        """Why this pack's rounds cannot run through ops.rnn_local_rounds: a
-        list of reasons, empty when they can."""
+        """Why this pack's rounds cannot run through ops.rnn_local_rounds
+        (or, see `rnn_batched_wide`, ops.rnn_wide_local_rounds): a list of
+        reasons, empty when they can."""
         from fedtorch_amd.components.datasets.device_cache import \
             DeviceCachedLoader
         why = []
@@ -509,7 +523,8 @@ class ClientPack(object):
                        'arena')
         else:
             try:
-                ops.rnn_layout_check(layout, self.base.arena.numel)
+                ops.rnn_layout_check(layout, self.base.arena.numel,
+                                     self.rnn_batched_wide())
             except ValueError as e:
                 why.append(str(e))
         why += self._run_blockers(

@@ -152,8 +152,9 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
     the federated type (`ClientPack.batched_correction`); and
     ops.rnn_local_rounds for the char-GRU (`rnn=True`:
     FEDTORCH_PACKED_BATCHED_RNN, `ClientPack.rnn_batched_eligible`, fedavg
-    only), with every client's own carried hidden state
-    (`ClientPack.rnn_state`).
+    only; ops.rnn_wide_local_rounds for 65 <= H <= 128 with
+    FEDTORCH_PACKED_BATCHED_RNN_WIDE on top), with every client's own carried
+    hidden state (`ClientPack.rnn_state`).
 
     The host first walks the counters (`_plan_local_rounds`).  `snap`:
     DRFA's [C, N] snapshot arena, row j receives client j's parameters before
@@ -174,7 +175,10 @@ def _batched_local_rounds(client, pack, server, online, snap, k_cut,
                dampening=g['dampening'], nesterov=g['nesterov'])
     corr = pack.batched_correction()
     if rnn:
-        loss = ops.rnn_local_rounds(
+        # looked up at the call: H <= 64 / 65 <= H <= 128
+        op = ops.rnn_wide_local_rounds if pack.rnn_batched_wide() \
+            else ops.rnn_local_rounds
+        loss = op(
             *operands, *pack.rnn_state(), layout=pack.rnn_layout(),
             wd_numel=client.arena.wd_numel, **sgd)
     elif cnn:

@@ -17,7 +17,12 @@ two device synchronisations (it includes the host's plan walk, the
 aggregation and the replica re-sync, which both paths share).  The full range
 of each path is printed.  The two paths agree only up to the hidden state:
 the slot loop threads the shared module's state through the clients, the
-batched round carries one per client."""
+batched round carries one per client.
+
+--hidden H runs the same at another hidden size; 65 <= H <= 128 times
+ops.rnn_wide_local_rounds (hip/rnnround_wide.h, both opt-ins) against the
+slot loop on the register-resident sequence kernels
+(FEDTORCH_FUSED_GRU_WIDE)."""
 import argparse
 import os
 import statistics
@@ -27,6 +32,7 @@ import time
 
 os.environ['FEDTORCH_FUSED_GRU'] = '1'
 os.environ['FEDTORCH_FUSED_GRU_TOKENS'] = '1'
+os.environ['FEDTORCH_FUSED_GRU_WIDE'] = '1'     # read for 65 <= H <= 128 only
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -38,7 +44,7 @@ from fedtorch_amd.parallel import multiclient  # noqa: E402
 B, TAU = 10, 10
 
 
-def federation(C):
+def federation(C, H):
     from fedtorch_amd.parameters import get_args
     from fedtorch_amd.nodes import Client
     from fedtorch_amd.components.datasets.device_cache import \
@@ -47,6 +53,7 @@ def federation(C):
     torch.manual_seed(1)
     np.random.seed(1)
     argv = ['-d', 'shakespeare', '--iid_data', 'false', '-a', 'rnn',
+            '--rnn_hidden_size', str(H),
             '-f', 'true', '--federated_type', 'fedavg', '--num_comms', '1',
             '--clients_per_rank', str(C), '-b', str(B), '--lr', '0.05',
             '--federated_sync_type', 'local_step', '--local_step', str(TAU),
@@ -76,6 +83,7 @@ def one_round(client, pack, batched):
     from fedtorch_amd.trainings.packed import \
         train_and_validate_federated_packed
     multiclient._BATCHED_RNN_ENABLED = batched
+    multiclient._BATCHED_RNN_WIDE_ENABLED = batched
     assert pack.rnn_batched_eligible() == batched, pack.rnn_batched_blockers()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -89,7 +97,7 @@ def configuration(C, a):
     if not (torch.cuda.is_available() and ops.hip_available()):
         raise SystemExit('packed_rnn_micro needs a GPU and the built kernel '
                          'pack')
-    client, pack = federation(C)
+    client, pack = federation(C, a.hidden)
     for _ in range(max(a.warmup, 1)):
         for batched in (False, True):
             one_round(client, pack, batched)
@@ -98,10 +106,11 @@ def configuration(C, a):
         for batched in (False, True):
             t[batched].append(one_round(client, pack, batched))
     s, f = t[False], t[True]
-    print('rnn shakespeare fedavg V=86 H=50 T=50 B=%d tau=%d C=%d momentum=on'
+    print('rnn shakespeare fedavg V=86 H=%d T=50 B=%d tau=%d C=%d momentum=on'
           ' ms/round: slot loop [%.2f, %.2f] median %.2f | batched [%.2f, '
           '%.2f] median %.2f | %s; median ratio %.1f' % (
-              B, TAU, C, min(s), max(s), statistics.median(s), min(f), max(f),
+              a.hidden, B, TAU, C, min(s), max(s), statistics.median(s),
+              min(f), max(f),
               statistics.median(f),
               'disjoint, below' if max(f) < min(s) else
               'disjoint, above' if min(f) > max(s) else 'overlap',
@@ -113,6 +122,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--clients', type=str, default='16,128')
+    ap.add_argument('--hidden', type=int, default=50)
     ap.add_argument('--single', action='store_true',
                     help='run the one configuration named by --clients in '
                          'this process')
@@ -123,7 +133,8 @@ def main():
     for C in a.clients.split(','):
         subprocess.run([sys.executable, os.path.abspath(__file__), '--single',
                         '--clients', C, '--rounds', str(a.rounds),
-                        '--warmup', str(a.warmup)], check=True)
+                        '--warmup', str(a.warmup), '--hidden',
+                        str(a.hidden)], check=True)
     print('PACKED_RNN_MICRO_OK')
 
 
