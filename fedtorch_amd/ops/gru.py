@@ -16,9 +16,18 @@ Hidden sizes 65..128 (``gru_wide_eligible``) take the same route over
 ``gru_wide_fwd`` / ``gru_wide_bwd`` (hip/gru_wide.h: W_hh resident in
 registers instead of LDS) when ``FEDTORCH_FUSED_GRU_WIDE=1`` is set as well.
 
+Hidden sizes 129..256 (``gru_stream_eligible``) take it over
+``gru_stream_fwd`` / ``gru_stream_bwd`` (hip/gru_stream.h: W_hh is too large
+for one workgroup's registers or LDS there, so every step streams it from
+global memory -- L2 after the first step -- into the MFMA B fragments) when
+``FEDTORCH_FUSED_GRU_STREAM=1`` is set on top of ``FEDTORCH_FUSED_GRU=1``.
+Within each 16-deep block of the recurrent sums these kernels add in another
+order than the two above; results are deterministic all the same.
+
 Every other call -- the flag off, a CPU tensor, a GRU the kernels do not
-cover (hidden_size > 128 among them) -- is exactly ``gru(x, h0)``.  Both
+cover (hidden_size > 256 among them) -- is exactly ``gru(x, h0)``.  All
 flags default OFF; timings against the library path: profiles/gru_notes.md.
+The token path below stops at hidden size 128.
 
 Token input (``gru_tok_seq(encoder, gru, tok, h0)``, third opt-in
 ``FEDTORCH_FUSED_GRU_TOKENS=1`` on top of the flags above, default OFF).  When
@@ -57,11 +66,14 @@ from fedtorch_amd import ops
 _GRU_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU', '0') == '1'
 # second opt-in on top of the first: hidden sizes MAX_H + 1 .. MAX_H_WIDE
 _GRU_WIDE_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU_WIDE', '0') == '1'
+# opt-in on top of the first: hidden sizes MAX_H_WIDE + 1 .. MAX_H_STREAM
+_GRU_STREAM_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU_STREAM', '0') == '1'
 # third opt-in on top of those: token input through the [V, 3H] table
 _GRU_TOK_ENABLED = os.environ.get('FEDTORCH_FUSED_GRU_TOKENS', '0') == '1'
 
 MAX_H = 64
 MAX_H_WIDE = 128
+MAX_H_STREAM = 256
 _FLOATS = (torch.bfloat16, torch.float32)
 
 
@@ -117,6 +129,20 @@ class _GRUWideSeqFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dout):
         return _seq_backward(ctx, ops._C.gru_wide_bwd, dout)
+
+
+class _GRUStreamSeqFn(torch.autograd.Function):
+    """the same over gru_stream_fwd / gru_stream_bwd (129 <= H <= 256)"""
+
+    @staticmethod
+    def forward(ctx, gx, w_hh, b_hh, h0, need):
+        return _seq_forward(ctx, ops._C.gru_stream_fwd, gx, w_hh, b_hh, h0,
+                            need)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        return _seq_backward(ctx, ops._C.gru_stream_bwd, dout)
 
 
 def _tok_forward(ctx, fwd, P, tok, w_hh, b_hh, h0, need):
@@ -224,6 +250,14 @@ def gru_wide_eligible(gru, x, h0):
     return _GRU_WIDE_ENABLED and _covered(gru, x, h0, MAX_H + 1, MAX_H_WIDE)
 
 
+def gru_stream_eligible(gru, x, h0):
+    """the streamed-weight kernels (MAX_H_WIDE < hidden_size <= MAX_H_STREAM)
+    apply to this call: the conditions of ``gru_eligible`` with that range,
+    and FEDTORCH_FUSED_GRU_STREAM=1 on top of FEDTORCH_FUSED_GRU=1"""
+    return _GRU_STREAM_ENABLED and _covered(gru, x, h0, MAX_H_WIDE + 1,
+                                            MAX_H_STREAM)
+
+
 def gru_seq(gru, x, h0):
     """``gru(x, h0)`` -> ``(out [B, T, H], h_n [1, B, H])``.  With
     FEDTORCH_FUSED_GRU=1 and an eligible call (GPU, one unidirectional
@@ -232,11 +266,15 @@ def gru_seq(gru, x, h0):
     launch, in training and eval; ``out`` and ``h_n = out[:, -1]`` are then
     fp32 whatever autocast says (module docstring).  With
     FEDTORCH_FUSED_GRU_WIDE=1 as well, 65 <= hidden_size <= 128 takes the
-    same route over gru_wide_fwd / gru_wide_bwd."""
+    same route over gru_wide_fwd / gru_wide_bwd, and with
+    FEDTORCH_FUSED_GRU_STREAM=1 129 <= hidden_size <= 256 takes it over
+    gru_stream_fwd / gru_stream_bwd."""
     if gru_eligible(gru, x, h0):
         fn = _GRUSeqFn
     elif gru_wide_eligible(gru, x, h0):
         fn = _GRUWideSeqFn
+    elif gru_stream_eligible(gru, x, h0):
+        fn = _GRUStreamSeqFn
     else:
         return gru(x, h0)
     with torch.autocast(device_type='cuda', enabled=False):

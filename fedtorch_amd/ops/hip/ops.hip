@@ -21,6 +21,7 @@
 #include "head.h"
 #include "gru.h"
 #include "gru_wide.h"
+#include "gru_stream.h"
 #include "gru_tok.h"
 #include "linearround.h"
 #include "mlpround.h"
@@ -2565,6 +2566,104 @@ std::vector<torch::Tensor> gru_wide_bwd(torch::Tensor dout, torch::Tensor out,
 }
 
 // --------------------------------------------------------------------------
+// 129 <= H <= 256: W_hh streamed from global memory in every step
+// (gru_stream.h).  Operand contracts, checks and return layouts are those of
+// gru_fwd / gru_bwd.
+// --------------------------------------------------------------------------
+static void gru_stream_check_dims(const char* who, long B, long T, long H) {
+  TORCH_CHECK(H >= GRU_STREAM_MINH && H <= GRU_STREAM_MAXH, who,
+              ": unsupported H=", H, " (129 <= H <= 256)");
+  TORCH_CHECK(B >= 1 && T >= 1, who, ": empty input");
+  TORCH_CHECK(B < (1L << 31) && T < (1L << 31) &&
+                  B * T < (1L << 40), who, ": input too large");
+}
+
+#define GRU_STREAM_SWITCH(H, LAUNCH)   \
+  switch (((H) + 15) / 16) {           \
+    case 9: LAUNCH(9); break;          \
+    case 10: LAUNCH(10); break;        \
+    case 11: LAUNCH(11); break;        \
+    case 12: LAUNCH(12); break;        \
+    case 13: LAUNCH(13); break;        \
+    case 14: LAUNCH(14); break;        \
+    case 15: LAUNCH(15); break;        \
+    default: LAUNCH(16); break;        \
+  }
+
+std::vector<torch::Tensor> gru_stream_fwd(torch::Tensor gx,
+                                          torch::Tensor w_hh,
+                                          torch::Tensor b_hh,
+                                          torch::Tensor h0, bool save_gates) {
+  const char* who = "gru_stream_fwd";
+  TORCH_CHECK(gx.is_cuda() && gx.dim() == 3 && gx.is_contiguous(), who,
+              ": gx must be contiguous [B, T, 3H] on GPU");
+  TORCH_CHECK(gx.scalar_type() == torch::kFloat, who, ": gx must be fp32");
+  TORCH_CHECK(gx.size(2) % 3 == 0, who, ": gx is ", gx.sizes(),
+              ", expected [B, T, 3H]");
+  const long B = gx.size(0), T = gx.size(1), H = gx.size(2) / 3;
+  gru_stream_check_dims(who, B, T, H);
+  const auto dev = gx.device();
+  gru_check_param(who, "w_hh", w_hh, {3 * H, H}, dev);
+  gru_check_param(who, "b_hh", b_hh, {3 * H}, dev);
+  gru_check_f32(who, "h0", h0, {B, H}, dev);
+  auto out = torch::empty({B, T, H}, gx.options());
+  auto gates = save_gates ? torch::empty({B, T, 4, H}, gx.options())
+                          : torch::empty({0}, gx.options());
+  const int wbf = w_hh.scalar_type() == torch::kBFloat16;
+  const int bbf = b_hh.scalar_type() == torch::kBFloat16;
+  // 16-byte (fp32) / 8-byte (bf16) weight loads: every four-element group of
+  // every row must be aligned, i.e. H a multiple of 4 and the base aligned
+  const int wvec =
+      H % 4 == 0 &&
+      reinterpret_cast<uintptr_t>(w_hh.data_ptr()) % (wbf ? 8 : 16) == 0;
+  const unsigned grid = (unsigned)((B + GRU_ROWS - 1) / GRU_ROWS);
+#define GRU_FWD_LAUNCH(NT)                                                   \
+  hipLaunchKernelGGL(gru_fwd_stream_k<NT>, dim3(grid), dim3(NT * WAVE), 0,   \
+                     STREAM, gx.data_ptr<float>(), w_hh.data_ptr(), wbf,     \
+                     wvec, b_hh.data_ptr(), bbf, h0.data_ptr<float>(),       \
+                     out.data_ptr<float>(),                                  \
+                     save_gates ? gates.data_ptr<float>() : nullptr, (int)B, \
+                     (int)T, (int)H)
+  GRU_STREAM_SWITCH(H, GRU_FWD_LAUNCH)
+#undef GRU_FWD_LAUNCH
+  return {out, gates};
+}
+
+std::vector<torch::Tensor> gru_stream_bwd(torch::Tensor dout,
+                                          torch::Tensor out,
+                                          torch::Tensor gates,
+                                          torch::Tensor w_hh,
+                                          torch::Tensor h0) {
+  const char* who = "gru_stream_bwd";
+  TORCH_CHECK(out.is_cuda() && out.dim() == 3 && out.is_contiguous(), who,
+              ": out must be contiguous [B, T, H] on GPU");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat, who, ": out must be fp32");
+  const long B = out.size(0), T = out.size(1), H = out.size(2);
+  gru_stream_check_dims(who, B, T, H);
+  const auto dev = out.device();
+  gru_check_f32(who, "dout", dout, {B, T, H}, dev);
+  gru_check_f32(who, "gates", gates, {B, T, 4, H}, dev);
+  gru_check_param(who, "w_hh", w_hh, {3 * H, H}, dev);
+  gru_check_f32(who, "h0", h0, {B, H}, dev);
+  auto dgx = torch::empty({B, T, 3 * H}, out.options());
+  auto dgh = torch::empty({B, T, 3 * H}, out.options());
+  auto dh0 = torch::empty({B, H}, out.options());
+  const int wbf = w_hh.scalar_type() == torch::kBFloat16;
+  const unsigned grid = (unsigned)((B + GRU_ROWS - 1) / GRU_ROWS);
+#define GRU_BWD_LAUNCH(NT)                                                   \
+  hipLaunchKernelGGL(gru_bwd_stream_k<NT>, dim3(grid), dim3(NT * WAVE), 0,   \
+                     STREAM, dout.data_ptr<float>(), out.data_ptr<float>(),  \
+                     gates.data_ptr<float>(), w_hh.data_ptr(), wbf,          \
+                     h0.data_ptr<float>(), dgx.data_ptr<float>(),            \
+                     dgh.data_ptr<float>(), dh0.data_ptr<float>(), (int)B,   \
+                     (int)T, (int)H)
+  GRU_STREAM_SWITCH(H, GRU_BWD_LAUNCH)
+#undef GRU_BWD_LAUNCH
+  return {dgx, dgh, dh0};
+}
+#undef GRU_STREAM_SWITCH
+
+// --------------------------------------------------------------------------
 // token input: gx[b, t] = P[tok[b, t]] gathered inside the forward kernels
 // (gru.h / gru_wide.h, TOK variant) and the one-launch parameter-gradient
 // reduce (gru_tok.h).  tok is never read on the host: a token outside [0, V)
@@ -3601,6 +3700,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_bwd", &gru_bwd);
   m.def("gru_wide_fwd", &gru_wide_fwd);
   m.def("gru_wide_bwd", &gru_wide_bwd);
+  m.def("gru_stream_fwd", &gru_stream_fwd);
+  m.def("gru_stream_bwd", &gru_stream_bwd);
   m.def("gru_tok_fwd", &gru_tok_fwd);
   m.def("gru_tok_wide_fwd", &gru_tok_wide_fwd);
   m.def("gru_tok_grads", &gru_tok_grads, py::arg("dgx"), py::arg("dgh"),

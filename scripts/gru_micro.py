@@ -2,7 +2,9 @@
 """Char-GRU sequence layer: FEDTORCH_FUSED_GRU off (nn.GRU, the library RNN
 path) vs on (one F.linear + the persistent gru_fwd / gru_bwd kernels of
 hip/gru.h).  With --hidden 65..128 --wide 1 the fused setting also turns on
-FEDTORCH_FUSED_GRU_WIDE (gru_wide_fwd / gru_wide_bwd of hip/gru_wide.h).
+FEDTORCH_FUSED_GRU_WIDE (gru_wide_fwd / gru_wide_bwd of hip/gru_wide.h), with
+--hidden 129..256 --stream 1 FEDTORCH_FUSED_GRU_STREAM (gru_stream_fwd /
+gru_stream_bwd of hip/gru_stream.h).
 Needs a GPU.
 
 (a) per call: forward + backward of the GRU layer alone (fp32, H = --hidden
@@ -103,6 +105,7 @@ def set_flags(flag, a):
     fused, tokens = flag if isinstance(flag, tuple) else (flag, False)
     fgru._GRU_ENABLED = fused
     fgru._GRU_WIDE_ENABLED = fused and bool(a.wide)
+    fgru._GRU_STREAM_ENABLED = fused and bool(a.stream)
     fgru._GRU_TOK_ENABLED = tokens
 
 
@@ -214,16 +217,22 @@ def main():
     ap.add_argument('--launches', type=int, default=1)
     ap.add_argument('--hidden', type=int, default=H)
     ap.add_argument('--wide', type=int, default=0)
+    ap.add_argument('--stream', type=int, default=0)
     ap.add_argument('--tokens', type=int, default=0)
     a = ap.parse_args()
     if a.tokens:
         SETTINGS.append(('tokens', (True, True)))
-    if a.hidden > (fgru.MAX_H_WIDE if a.wide else fgru.MAX_H):
+    covered = a.hidden <= fgru.MAX_H or \
+        (a.wide and a.hidden <= fgru.MAX_H_WIDE) or \
+        (a.stream and fgru.MAX_H_WIDE < a.hidden <= fgru.MAX_H_STREAM)
+    if not covered or (a.tokens and a.hidden > fgru.MAX_H_WIDE):
         raise SystemExit('H = %d is the library path either way (--wide 1 '
-                         'covers 65..128)' % a.hidden)
+                         'covers 65..128, --stream 1 129..256 without '
+                         '--tokens)' % a.hidden)
     if not (torch.cuda.is_available() and ops.hip_available()):
         raise SystemExit('gru_micro needs a GPU and the built kernel pack')
-    old = (fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED, fgru._GRU_TOK_ENABLED)
+    old = (fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED, fgru._GRU_TOK_ENABLED,
+           fgru._GRU_STREAM_ENABLED)
     try:
         if a.tokens:
             reduce_alone(a)
@@ -232,8 +241,8 @@ def main():
             layer(a)
         train_step(a)
     finally:
-        (fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED,
-         fgru._GRU_TOK_ENABLED) = old
+        (fgru._GRU_ENABLED, fgru._GRU_WIDE_ENABLED, fgru._GRU_TOK_ENABLED,
+         fgru._GRU_STREAM_ENABLED) = old
     print('GRU_MICRO_OK')
 
 
