@@ -12,7 +12,7 @@ padding games) so MIOpen picks NHWC kernels under bf16 autocast on gfx950.
 import torch
 import torch.nn as nn
 
-from fedtorch_amd.ops.batchnorm import BNReLU, BNAddReLU
+from fedtorch_amd.ops.batchnorm import BNReLU, BNAddReLU, grad_fork
 from fedtorch_amd.ops.conv3x3 import conv_bn_act
 from fedtorch_amd.ops.head import pool_fc
 
@@ -50,7 +50,11 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
-        identity = x if self.downsample is None else self.downsample(x)
+        # x feeds conv1 and the shortcut: on the training kernel path the
+        # add of their two gradients runs inside the producing BN's backward
+        # statistics kernel (ops/batchnorm.py grad_fork); else xs is x
+        x, xs = grad_fork(x, self.training)
+        identity = xs if self.downsample is None else self.downsample(xs)
         # conv_bn_act == bn(conv(x)[, identity]); in eval under no_grad each
         # pair is one fused conv+BN(+add)+ReLU launch (ops/conv3x3.py)
         out = conv_bn_act(self.conv1, self.bn1, x)

@@ -9,12 +9,25 @@ inference kernel (bn_fwd_eval, one launch incl. residual + ReLU; flag
 FEDTORCH_MFMA_EVAL in ops/conv3x3.py); eval with grad, NCHW eval and CPU
 fall back to the stock nn.BatchNorm2d path; state_dict layout is unchanged.
 """
+import os
+
 import torch
 import torch.nn as nn
 
 from fedtorch_amd import ops
 
 _VN = {torch.bfloat16: 8, torch.float32: 4, torch.float64: 2}
+# Fork backward (hip/batchnorm.h bnh_fork_stats_k): where a fused BN's
+# output has two consumers (a BasicBlock's conv1 and its shortcut), the BN's
+# statistics kernel adds the two incoming gradients itself and stores the
+# masked sum g once; g is the dy of the dx pass, the residual's gradient
+# and what the engine's add would have produced: 2 launches and 8 tensor
+# passes per fork instead of 3 and 14, bit-identical gradients.  Handshake:
+# _GradFork.backward registers the partial rows under g's data_ptr,
+# _FusedBNFunction.backward pops them (the `_BNBWD_TAGS` pattern of
+# ops/conv3x3.py).  Default and figures: profiles/bn_fork_notes.md.
+_FORK_ENABLED = os.environ.get('FEDTORCH_BN_FORK', '1') == '1'
+_FORK_TAGS = {}
 
 
 def _is_cl(x):
@@ -78,6 +91,20 @@ class _FusedBNFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        # fork handshake: dy is the masked sum g of _GradFork.backward and
+        # its partial rows wait under its data_ptr.  A tag of another node
+        # (a stale ptr) is never applied; without one, bn_bwd below masks g
+        # again, which changes nothing.
+        tag = _FORK_TAGS.pop(dy.data_ptr(), None) if _FORK_TAGS else None
+        if tag is not None and tag[0] is ctx:
+            x, weight, save_mean, save_ivar = ctx.saved_tensors[:4]
+            dx, dweight, dbias = ops._C.bn_bwd_part(
+                dy, x, tag[1], save_mean, save_ivar,
+                weight if weight is not None
+                else torch.empty(0, device=x.device))
+            return (dx, dweight if weight is not None else None,
+                    dbias if weight is not None else None, None, None,
+                    None, None, None, dy if ctx.has_res else None, None)
         mask = None
         if ctx.has_mask:
             x, weight, save_mean, save_ivar, mask = ctx.saved_tensors
@@ -124,6 +151,68 @@ class _FusedBNFunction(torch.autograd.Function):
         return (dx, dweight if weight is not None else None,
                 dbias if weight is not None else None, None, None, None,
                 None, None, dres if ctx.has_res else None, None)
+
+
+class _GradFork(torch.autograd.Function):
+    """(t, t) of a tensor with two consumers: the identity in forward; the
+    backward adds the two gradients.  `node` (or None) is the
+    _FusedBNFunction node that produced t: with it the sum, that BN's ReLU
+    mask and its backward statistics are one bn_bwd_fork_stats launch."""
+
+    @staticmethod
+    def forward(ctx, t, node):
+        ctx.set_materialize_grads(False)
+        ctx.node = node
+        return t.view_as(t), t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        a, b = (g1, g2) if g1 is not None else (g2, None)
+        if a is None:
+            return None, None
+        node = ctx.node
+        saved = node.saved_tensors if node is not None else None
+        x = saved[0] if saved else None
+        if x is None or not all(
+                g is None or (g.is_cuda and g.dtype == x.dtype
+                              and g.shape == x.shape and _is_cl(g))
+                for g in (a, b)):
+            # the engine's own add: a gradient in another layout or dtype
+            return (a if b is None else a + b), None
+        empty = torch.empty(0, device=x.device)
+        empty_mask = torch.empty(0, device=x.device, dtype=torch.uint8)
+        g, part = ops._C.bn_bwd_fork_stats(
+            a, b if b is not None else empty, x,
+            saved[4] if node.relu and not node.has_mask else empty,
+            saved[4] if node.has_mask else empty_mask,
+            saved[2], saved[3], node.relu)
+        _FORK_TAGS[g.data_ptr()] = (node, part)
+        return g, None
+
+
+def fork_ok(enabled, training, grad_on, kernels, cl, nhwc, defer, from_bn):
+    """the fork path's conditions, all of them: the flag, a training module
+    under grad mode, the kernel route active, a channels_last tensor of an
+    NHWC-eligible dtype and C, the deferred BN backward off, and a tensor
+    that is the output of a fused channels_last BN"""
+    return bool(enabled and training and grad_on and kernels and cl
+                and nhwc and not defer and from_bn)
+
+
+def grad_fork(x, training):
+    """(x, x) for the two consumers of a block input.  On the training
+    kernel path, with x the output of a _FusedBNFunction, the pair comes
+    from _GradFork; anything else gets x itself twice."""
+    from fedtorch_amd.ops import conv3x3 as _c3
+    node = x.grad_fn
+    from_bn = (getattr(node, '_forward_cls', None) is _FusedBNFunction
+               and node.nhwc)
+    if not fork_ok(_FORK_ENABLED, training, torch.is_grad_enabled(),
+                   _c3._kernels_active(x), _is_cl(x),
+                   x.dim() == 4 and _nhwc_ok(x.shape[1], x.dtype),
+                   _c3.bn_defer_active(), from_bn):
+        return x, x
+    return _GradFork.apply(x, node)
 
 
 class FusedBatchNorm2d(nn.BatchNorm2d):

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include "common.h"
 #include <hip/hip_bf16.h>
+#include <type_traits>
 
 // ---- 16-byte vectorized element types ------------------------------------
 template <typename T> struct BnVec;
@@ -474,6 +475,106 @@ __global__ void bnh_bwd_stats_k(const T* __restrict__ dy,
           if ((float)yy.d[j] <= 0.f) g.d[j] = (T)0.f;
       }
     }
+#pragma unroll
+    for (int j = 0; j < VN; ++j) {
+      float gg = (float)g.d[j];
+      float xh = ((float)xv.d[j] - mean[j]) * ivar[j];
+      s1[j] += gg;
+      s2[j] = fmaf(gg, xh, s2[j]);
+    }
+  }
+  for (int off = WAVE / 2; off >= cgc; off >>= 1) {
+#pragma unroll
+    for (int j = 0; j < VN; ++j) {
+      s1[j] += __shfl_xor(s1[j], off, WAVE);
+      s2[j] += __shfl_xor(s2[j], off, WAVE);
+    }
+  }
+  __shared__ float lds[2][FT_BLOCK / WAVE][256];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  if (lane < cgc) {
+#pragma unroll
+    for (int j = 0; j < VN; ++j) {
+      lds[0][wid][lane * VN + j] = s1[j];
+      lds[1][wid][lane * VN + j] = s2[j];
+    }
+  }
+  __syncthreads();
+  const int c = threadIdx.x;
+  if (c < C) {
+    float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < FT_BLOCK / WAVE; ++w) {
+      a1 += lds[0][w][c];
+      a2 += lds[1][w][c];
+    }
+    float* p = part + ((long)blockIdx.x * C + c) * 2;
+    p[0] = a1;
+    p[1] = a2;
+  }
+}
+
+// bnh_bwd_stats_k at a fork of the network (a BN output with two
+// consumers): adds the two incoming gradients itself, s = (T)(a + b) with
+// the fp32 add and one rounding of the library's elementwise add (b may be
+// null: s = a), masks, STORES the masked sum to g and accumulates the
+// partial rows from it.  g then is the dy of the dx pass (relu = 0, no
+// y/mask read), the gradient of the fused residual, and what the autograd
+// engine's add would have produced.  Same grid, block, row-stride loop and
+// reduction text as bnh_bwd_stats_k, so given a + b that kernel writes the
+// same partial rows bit for bit.  Kept as a second text: a shared body
+// would change the ISA of the kernel above.
+template <typename T, typename VT, int VN>
+__global__ void bnh_fork_stats_k(const T* __restrict__ a,
+                                 const T* __restrict__ b,
+                                 const T* __restrict__ x,
+                                 const T* __restrict__ yv,
+                                 const unsigned char* __restrict__ mask,
+                                 const float* __restrict__ save_mean,
+                                 const float* __restrict__ save_ivar, long NI,
+                                 long C, int lgc, T* __restrict__ gout,
+                                 float* __restrict__ part /*[B,C,2]*/,
+                                 int relu) {
+  const int cgc = 1 << lgc;
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned cg = t & (cgc - 1);
+  const unsigned rstride = (gridDim.x * blockDim.x) >> lgc;
+  float mean[VN], ivar[VN];
+#pragma unroll
+  for (int j = 0; j < VN; ++j) {
+    mean[j] = save_mean[cg * VN + j];
+    ivar[j] = save_ivar[cg * VN + j];
+  }
+  float s1[VN], s2[VN];
+#pragma unroll
+  for (int j = 0; j < VN; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+  for (unsigned r = t >> lgc; r < NI; r += rstride) {
+    const long base = (long)r * C + cg * VN;
+    VT g = *reinterpret_cast<const VT*>(a + base);
+    VT xv = *reinterpret_cast<const VT*>(x + base);
+    if (b) {
+      VT bv = *reinterpret_cast<const VT*>(b + base);
+      // the library adds bf16 in fp32; fp32 and fp64 in their own type
+      using AT = std::conditional_t<std::is_same_v<T, double>, double, float>;
+#pragma unroll
+      for (int j = 0; j < VN; ++j)
+        g.d[j] = (T)((AT)g.d[j] + (AT)bv.d[j]);
+    }
+    if (relu) {
+      if (mask) {
+        const unsigned m = mask[((long)r * C >> 3) + cg];
+#pragma unroll
+        for (int j = 0; j < VN; ++j)
+          if (!((m >> j) & 1u)) g.d[j] = (T)0.f;
+      } else {
+        VT yy = *reinterpret_cast<const VT*>(yv + base);
+#pragma unroll
+        for (int j = 0; j < VN; ++j)
+          if ((float)yy.d[j] <= 0.f) g.d[j] = (T)0.f;
+      }
+    }
+    *reinterpret_cast<VT*>(gout + base) = g;
 #pragma unroll
     for (int j = 0; j < VN; ++j) {
       float gg = (float)g.d[j];

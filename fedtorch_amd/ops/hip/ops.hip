@@ -2124,6 +2124,115 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, torch::Tensor x,
   return {dx, dweight, dbias, dres};
 }
 
+// BN backward at a fork (a BN output with two consumers), first half:
+// g = relu_mask(a + b) and the partial rows of sum(g), sum(g * xhat) in ONE
+// bnh_fork_stats_k launch -- the engine's add of the two gradients, the
+// mask and the statistics pass in one read of a, b, x.  b empty: g =
+// relu_mask(a).  Channels_last only.  Returns {g, part [B, C, 2]}.
+std::vector<torch::Tensor> bn_bwd_fork_stats(
+    torch::Tensor a, torch::Tensor b, torch::Tensor x, torch::Tensor y,
+    torch::Tensor mask, torch::Tensor save_mean, torch::Tensor save_ivar,
+    bool relu) {
+  const char* who = "bn_bwd_fork_stats";
+  bn_check_x(who, x);
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), who,
+              ": channels_last only");
+  long N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(bnh_ok(C, bn_vn(x)), who, ": unsupported C=", C);
+  bn_check_like(who, "a", a, x, true);
+  if (conv_present(b)) bn_check_like(who, "b", b, x, true);
+  bn_check_vec(who, "save_mean", save_mean, C, false);
+  bn_check_vec(who, "save_ivar", save_ivar, C, false);
+  if (conv_present(mask)) {
+    // one bit per element over the flat NHWC index (see bn_bwd)
+    TORCH_CHECK(x.scalar_type() == torch::kBFloat16, who,
+                ": mask needs bf16 x");
+    TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kByte &&
+                    mask.is_contiguous() && mask.numel() == (N * HW * C) >> 3,
+                who, ": mask must be contiguous uint8 [N*HW*C/8] = [",
+                (N * HW * C) >> 3, "] on GPU");
+  }
+  TORCH_CHECK(!relu || conv_present(mask) || conv_present(y), who,
+              ": relu needs y/mask");
+  if (relu && !conv_present(mask)) bn_check_like(who, "y", y, x, true);
+  auto g = torch::empty_like(x);
+  torch::Tensor part;
+  AT_DISPATCH_FLOATING_TYPES_AND(at::ScalarType::BFloat16, x.scalar_type(),
+                                 "bnh_fork_stats", [&] {
+    using T = std::conditional_t<std::is_same_v<scalar_t, at::BFloat16>,
+                                 __hip_bfloat16, scalar_t>;
+    constexpr int VN = BnVec<T>::N;
+    const int lgc = bnh_lgc(C, VN);
+    const long NI = N * HW, tasks = NI << lgc;
+    const int B = bnh_red_grid(tasks);
+    part = torch::empty({B, C, 2}, x.options().dtype(torch::kFloat));
+    const unsigned char* mp =
+        (relu && mask.numel()) ? mask.data_ptr<unsigned char>() : nullptr;
+    const T* yp = (relu && !mp) ? reinterpret_cast<const T*>(y.data_ptr())
+                                : nullptr;
+    hipLaunchKernelGGL((bnh_fork_stats_k<T, typename BnVec<T>::V, VN>),
+                       dim3(B), dim3(FT_BLOCK), 0, STREAM,
+                       reinterpret_cast<const T*>(a.data_ptr()),
+                       b.numel() ? reinterpret_cast<const T*>(b.data_ptr())
+                                 : nullptr,
+                       reinterpret_cast<const T*>(x.data_ptr()), yp, mp,
+                       save_mean.data_ptr<float>(),
+                       save_ivar.data_ptr<float>(), NI, C, lgc,
+                       reinterpret_cast<T*>(g.data_ptr()),
+                       part.data_ptr<float>(), relu ? 1 : 0);
+  });
+  return {g, part};
+}
+
+// second half: dx, dweight, dbias from the masked gradient g and its
+// partial rows -- ONE launch of the unchanged bnh_bwd_dx_k with relu = 0
+// (no y/mask read: g is masked already) and no dres store (dres is g).
+std::vector<torch::Tensor> bn_bwd_part(
+    torch::Tensor g, torch::Tensor x, torch::Tensor part,
+    torch::Tensor save_mean, torch::Tensor save_ivar, torch::Tensor weight) {
+  const char* who = "bn_bwd_part";
+  bn_check_x(who, x);
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast), who,
+              ": channels_last only");
+  long N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(bnh_ok(C, bn_vn(x)), who, ": unsupported C=", C);
+  bn_check_like(who, "g", g, x, true);
+  TORCH_CHECK(part.is_cuda() && part.dim() == 3 && part.size(1) == C &&
+                  part.size(2) == 2 && part.scalar_type() == torch::kFloat &&
+                  part.is_contiguous(),
+              who, ": part must be contiguous [B, C, 2] fp32 on GPU");
+  TORCH_CHECK(part.size(0) >= 1 && part.size(0) <= 256, who,
+              ": part must have 1..256 rows, got ", part.size(0));
+  bn_check_vec(who, "save_mean", save_mean, C, false);
+  bn_check_vec(who, "save_ivar", save_ivar, C, false);
+  bn_check_vec(who, "weight", weight, C, true);
+  auto f32 = x.options().dtype(torch::kFloat);
+  auto dx = torch::empty_like(x);
+  auto dweight = torch::empty({C}, f32);
+  auto dbias = torch::empty({C}, f32);
+  AT_DISPATCH_FLOATING_TYPES_AND(at::ScalarType::BFloat16, x.scalar_type(),
+                                 "bnh_bwd_part", [&] {
+    using T = std::conditional_t<std::is_same_v<scalar_t, at::BFloat16>,
+                                 __hip_bfloat16, scalar_t>;
+    constexpr int VN = BnVec<T>::N;
+    const int lgc = bnh_lgc(C, VN);
+    const long NI = N * HW, tasks = NI << lgc;
+    hipLaunchKernelGGL((bnh_bwd_dx_k<T, typename BnVec<T>::V, VN>),
+                       dim3(bnh_ew_grid(tasks)), dim3(FT_BLOCK), 0, STREAM,
+                       reinterpret_cast<const T*>(g.data_ptr()),
+                       reinterpret_cast<const T*>(x.data_ptr()),
+                       (const T*)nullptr, (const unsigned char*)nullptr,
+                       part.data_ptr<float>(), (int)part.size(0),
+                       save_mean.data_ptr<float>(),
+                       save_ivar.data_ptr<float>(),
+                       weight.numel() ? weight.data_ptr<float>() : nullptr,
+                       reinterpret_cast<T*>(dx.data_ptr()), (T*)nullptr,
+                       dweight.data_ptr<float>(), dbias.data_ptr<float>(),
+                       NI, C, lgc, 0);
+  });
+  return {dx, dweight, dbias};
+}
+
 // deferred BN backward: stats + per-channel affine coefs (+ optional
 // dres); the elementwise dx pass moves into the consuming conv's staging
 std::vector<torch::Tensor> bn_bwd_defer(
@@ -3742,6 +3851,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_dgrad", &conv3x3_dgrad);
   m.def("conv3x3_dgrad_bn", &conv3x3_dgrad_bn);
   m.def("bn_bwd_defer", &bn_bwd_defer);
+  m.def("bn_bwd_fork_stats", &bn_bwd_fork_stats);
+  m.def("bn_bwd_part", &bn_bwd_part);
   m.def("conv3x3_bn_fwd", &conv3x3_bn_fwd);
   m.def("conv3x3s2_bn_fwd", &conv3x3s2_bn_fwd);
   m.def("conv3x3_bn_act_fwd", &conv3x3_bn_act_fwd);
